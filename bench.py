@@ -6,14 +6,23 @@ virtual-model wrench -> leg FK -> contact-force-distribution QP -> joint torques
 (clamped), through the C-ABI (qlamd_balance_solve_batch) with all inputs and
 outputs resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--gait static|trot] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--gait static|trot] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K = --steps steps as ONE timed region (ms_per_step = its wall time / K), writes
+the last timed step's efforts and statuses under DIR if --dump-outputs is given (DIR/tau.npy, DIR/status.npy, float64) and
+prints the line.  Its untimed work does not grow with K: a region of more than REGION_MAX steps is a chain of replays of one
+captured graph, and the replays before the timed region are one of each graph, about 150 ms of settling and PREROLL
+synchronised replays of at most REGION_MAX steps each.  Everything else
+the line can carry -- the median of --replays timed regions, the CPU baseline, the roofline and VALU figures (kernel time from
+a replay of its own), the statuses of every tick, the other methods, layouts, presets and sizes -- is measured only with
+--full.
 
 N = 1: BASELINE configs[1], batch = 4096 robots, static 4-contact stance with SURVEY.md 8(d)'s literal tracking errors
-       (0.02 m / 0.05 rad / 0.1); the same line carries an `also` object with every other BASELINE config measured in the
-       same process (static-calm and trot at 4096 robots, trot at 8192 and 65 536 robots, the pose SQP at 4096 problems, the
-       whole tick and the whole-body step at 4096 robots), each with its kernel time, roofline fraction and PMC provenance,
-       `cold_start` / `unplaced` (the same steps with every QP started from the empty working set, placed and through the
-       plain entry) and `scale_point` (8192 trot robots per GPU: the workload every line at every N carries).
+       (0.02 m / 0.05 rad / 0.1); with --full the same line carries an `also` object with every other BASELINE config
+       measured in the same process (static-calm and trot at 4096 robots, trot at 8192 and 65 536 robots, the pose SQP at
+       4096 problems, the whole tick and the whole-body step at 4096 robots), each with its kernel time, roofline fraction and
+       PMC provenance, `cold_start` / `unplaced` (the same steps with every QP started from the empty working set, placed and
+       through the plain entry) and `scale_point` (8192 trot robots per GPU: the workload every line at every N carries).
 Every timed region runs on a TRAJECTORY (synth.trajectory): the K captured steps solve K consecutive control ticks of the same
 robots (2.5 ms apart: poses integrated with the twists, a trot's gait phase advanced and its support flags recomputed, so
 about 1.1 % of the trot robots change their support set every tick), so that every placement and every warm start comes
@@ -27,6 +36,7 @@ parent never touches a GPU API and exits with the child's code).  Rank 0 prints 
 """
 import argparse
 import json
+import math
 import os
 import sys
 import threading
@@ -46,6 +56,26 @@ FP64_VALU_PEAK_TFLOPS = 78.6
 # A wave64 VALU instruction occupies its SIMD16 for 4 cycles, so insts * 4 / (SIMDs * kernel cycles) is the fraction
 # of the chip's VALU issue slots the launch used -- the resource this FP64 path is actually bound by.
 N_SIMD, SHADER_CLOCK_HZ = 1024, 2.4e9
+# Longest captured graph: a timed region of more steps is a chain of replays of one graph of about this many steps (and one
+# graph of the rest), so that neither capture nor the untimed replays before the timed region grow with --steps.
+REGION_MAX = 2000
+PREROLL = 10   # untimed, synchronised region replays before a plain run's one timed region (see measure())
+# --dump-outputs: 13 doubles per robot (12 efforts + status), so this many robots stay under 64 MB with their row index
+DUMP_MAX_ROBOTS, DUMP_SEED = 262144, 0
+
+
+def write_outputs(dirname, tau, status):
+    """--dump-outputs: the efforts (robots x 12) and statuses of one step as DIR/tau.npy and DIR/status.npy in float64.  Beyond
+    DUMP_MAX_ROBOTS robots, the same seeded sample of rows every run, their indices in DIR/robot_index.npy."""
+    import numpy as np
+    tau, status = np.asarray(tau, dtype=np.float64), np.asarray(status, dtype=np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    out = {"tau": tau, "status": status}
+    if len(tau) > DUMP_MAX_ROBOTS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(tau), DUMP_MAX_ROBOTS, replace=False))
+        out = {"tau": tau[rows], "status": status[rows], "robot_index": rows.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def source_hash():
@@ -185,10 +215,11 @@ def parse():
                     help="static stance tracking errors: survey = SURVEY.md 8(d)'s literal 0.02 m / 0.05 rad / 0.1 (default), "
                          "calm = 0.004 / 0.005 / 0.01 (a robot holding its pose: constraints mostly inactive, DESIGN.md 2)")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the `also` / `unplaced` / `scale_point` objects (the other presets, methods and configs)")
+                    help="with --full: skip the `also` / `unplaced` / `scale_point` objects (the other presets, methods and configs)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--replays", type=int, default=11,
-                    help="timed samples of exactly K steps each (barrier + synchronize on both sides); the median is reported")
+                    help="with --full: timed samples of exactly K steps each (barrier + synchronize on both sides); the median is "
+                         "reported.  A plain run times one sample")
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="untimed replays of the captured steps for this long before the timed samples: the shader clock of a GPU "
                          "that has just been idle keeps rising for the first ~10 ms of work (samples of K = 20 steps fell from "
@@ -237,7 +268,17 @@ def parse():
                          "placed / warm-started loop time, never the other way -- falls into one region in T / K")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the CPU baseline, kernel time with the "
+                         "roofline and VALU figures, the statuses and iteration counts of every tick, the other methods, layouts, "
+                         "presets and sizes (`also`, `scale_point`), and with several ranks the gather check and the run without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="balance workload: write what the last timed step computed -- the joint efforts (tau.npy, robots x 12) "
+                         "and statuses (status.npy) of every robot, float64 -- under DIR; beyond %d robots a fixed, seeded "
+                         "sample of them (robot_index.npy names the rows)" % DUMP_MAX_ROBOTS)
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "balance":
+        ap.error("--dump-outputs covers the balance workload (the headline) only")
     if args.batch is None:
         args.batch = 4096 if (args.gpus == 1 or args.workload != "balance") else 8192
     if args.gait is None:
@@ -384,7 +425,7 @@ def bench_pose_sqp(args):
     algo = 424 * B  # 46 doubles in + 7 out per pose-SQP solve
     achieved = algo / (kernel_ms * 1e-3) / 1e9
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the oracle (C restatement, kind "port") on the host cores: same problems, 5 iterations, bounded sample
         from oracle import oracle as O
         visible = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -467,7 +508,7 @@ def bench_wholebody(args):
     rec, traffic_src = pmc_record(kname, B, ("wholebody-" + gait) if solve else "wholebody_dynamics")
     traffic = int(rec["fetch_bytes"] + rec["write_bytes"]) if rec and "fetch_bytes" in rec and "write_bytes" in rec else None
     cpu = None
-    if solve and not args.no_cpu_baseline:
+    if solve and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         visible = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
         os.environ.setdefault("OMP_WAIT_POLICY", "passive")
@@ -556,7 +597,7 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     # rank 0 at N = 1 only: the CPU baseline, in a pinned child process, BEFORE this process touches the GPU
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and args.workload == "balance":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "balance":
         try:
             cpu = cpu_baseline(args.gait, args.errors, args.batch, args.cpu_seconds)
         except Exception as e:  # the GPU measurement must not be lost to a failing host-side probe
@@ -606,9 +647,10 @@ def main():
     trajectories = {}   # (gait, errors, batch, ticks, rank) -> (device-resident states of every tick, support switches per tick)
 
     def run_preset(gait, errors, with_gather, replays, second_without_gather, collect="rccl", every=1, batch=None,
-                   method="plain", records=False):
+                   method="plain", records=False, keep_last=False):
         """One workload preset on this rank's shard: warm-up, K steps captured as one hipGraph, `replays` timed samples.
         every: steps per collection; collect: "rccl" (all-gather) or "peer" (copies into the peers' buffers).
+        keep_last: res["last"] = (efforts, statuses) of the last step of the last timed sample, on this rank's device.
         Step k of the loop solves tick k % T of a T-tick trajectory of the shard's robots (synth.trajectory).  method "placed": the caller's loop of include/qlamd.h -- step k runs in order[k & 1], writes
         iters[k & 1] and makes order[(k + 1) & 1] from iters[(k - 1) & 1]: tick k runs in the placement made during tick
         k - 1 from the counts of tick k - 2; "warm": the same, and every robot's QP starts from its final working set of tick
@@ -622,6 +664,17 @@ def main():
         cap = 200 if B <= 16384 else 64
         T = max(1, args.ticks) if args.ticks else (cap if K >= cap else K * max(1, cap // K))
         NG = max(1, -(-T // K)) if K > 0 else 1
+        G = max(1, every)
+        # A region of more than REGION_MAX steps is replayed as a chain: `reps` replays of one graph of L steps -- L a multiple of
+        # T and of G, so that every replay continues the trajectory and ends on a collection boundary -- then one graph of the
+        # remaining steps.  parts: the (first, last + 1) step indices each graph of a region is captured with, in replay order.
+        L = K
+        if K > REGION_MAX:
+            unit = T * G // math.gcd(T, G)
+            L = unit * max(1, REGION_MAX // unit)
+        reps, rest = divmod(K, L) if K > 0 else (1, 0)
+        parts = [(0, L)] * reps + ([(reps * L, K)] if rest else [])
+        last_k = parts[-1][1] - 1 if K > 0 else 0      # the index the region's last step is captured with
         # rank r owns robots [r*B, (r+1)*B) of the global batch (contiguous shards)
         # records: the double fields of a robot in one 48-double record (QLAMD_OPT_STATE_LAYOUT = QLAMD_STATE_RECORDS) instead of
         # one array per field -- what a permuted launch gathers in three lines instead of nine
@@ -654,7 +707,6 @@ def main():
                                                 policy=capi.PLACEMENT_AUTO, stream=st)
             else:
                 ctx.balance_solve_device(ds[k % T], out, None, status, stream=st)
-        G = max(1, every)
         status = torch.full((B,), -1, dtype=torch.int32, device=dev)
         peer = PeerBuffers(G * B * 12, rank, world, dev, dist, torch) if (with_gather and collect == "peer") else None
         gathered = ([torch.zeros(world, G, B, 12, dtype=torch.float64, device=dev) for _ in range(2)]
@@ -702,8 +754,8 @@ def main():
         # hipGraph (solves on one stream, gathers on a second one) and replayed: a step is a few tens of microseconds,
         # comparable to one eager launch from Python.  If capture fails the steps are launched eagerly, the all-gather
         # of step k then overlapping the solve of step k+1.
-        def capture(wg, g):
-            """steps g K .. g K + K - 1 of the loop (ticks (g K + j) % T) as one graph"""
+        def capture(wg, g, first, stop):
+            """steps g K + first .. g K + stop - 1 of the loop (ticks (g K + j) % T) as one graph"""
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -720,7 +772,7 @@ def main():
                     overlap = wg and (world > 1 or args.overlap_gather)
                     comm = torch.cuda.Stream() if overlap else None
                     gathered_ev = [None, None]
-                    for k in range(args.steps):
+                    for k in range(first, stop):
                         buf = (k // G) & 1
                         if overlap and k % G == 0 and gathered_ev[buf] is not None:
                             side.wait_event(gathered_ev[buf])
@@ -751,10 +803,13 @@ def main():
             graphs, overlap = None, False
             if not args.no_graph:
                 try:
-                    graphs = []
+                    graphs = []   # per region: its graphs in replay order (a chain replays one graph `reps` times)
                     for g in range(NG):
-                        gr, overlap = capture(wg, g)
-                        graphs.append(gr)
+                        made = {}
+                        for part in parts:
+                            if part not in made:
+                                made[part], overlap = capture(wg, g, *part)
+                        graphs.append([made[part] for part in parts])
                 except Exception as e:  # pragma: no cover - fall back to eager launches
                     sys.stderr.write("hipGraph capture failed (%s); eager launches\n" % e)
                     graphs = None
@@ -771,32 +826,52 @@ def main():
             turn = [0]
 
             def replay():   # the next K steps of the loop
-                graphs[turn[0] % NG].replay()
+                for gr in graphs[turn[0] % NG]:
+                    gr.replay()
                 turn[0] += 1
 
+            def settle_replay():   # untimed: one region, or one graph of L steps of a chain (L steps continue the trajectory)
+                if len(parts) > 1:
+                    graphs[turn[0] % NG][0].replay()
+                else:
+                    replay()
+
             if graphs is not None:
-                for _ in range(NG):
-                    replay()  # one untimed replay of each (instantiation / upload)
+                for region in graphs:
+                    for gr in {id(gr): gr for gr in region}.values():
+                        gr.replay()  # one untimed replay of each graph (instantiation / upload)
                 fence()
                 # ... and untimed replays until the clocks have settled (every rank the same number: no host clock involved
                 # in the count once it is agreed on)
                 t_one = time.perf_counter()
-                replay()
+                settle_replay()
                 fence()
                 t_one = max(time.perf_counter() - t_one, 1e-5)
                 n_settle = int(min(2000, max(0.0, args.settle_ms * 1e-3) / t_one))
-                n_settle += (-(turn[0] + n_settle)) % NG      # the first timed region starts at tick 0
+                # --full: the first timed region starts at tick 0.  Without --full the one timed region is the middle one of the
+                # trajectory where there are several, the farthest from the jump back to tick 0 and the ticks that recover from it.
+                # A plain run's one timed region follows PREROLL untimed ones, each between synchronisations like a timed
+                # sample: the first replay after the back-to-back settling is slow (measured up to 3x at K = 20), and --full's
+                # median of 11 samples leaves it out the same way.
+                n_pre = 0 if args.full else PREROLL
+                first_region = 0 if args.full else NG // 2
+                n_settle += (first_region - (turn[0] + n_settle + (n_pre if len(parts) == 1 else 0))) % NG
                 if collective:
                     nt = torch.tensor([n_settle], dtype=torch.int32, device=dev)
                     dist.all_reduce(nt, op=dist.ReduceOp.MAX)
                     n_settle = int(nt.item())
                 for _ in range(n_settle):
-                    replay()
+                    settle_replay()
                 fence()
+                for _ in range(n_pre):
+                    settle_replay()
+                    fence()
 
-            def sample():
+            last = []
+
+            def sample(final):
                 """One timed region: exactly K steps between barrier + synchronize on both sides.  Returns (wall seconds,
-                mean solve-kernel ms from HIP events on the launch stream)."""
+                mean solve-kernel ms from HIP events on the launch stream, or None: measured with --full only)."""
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev, pending = [], []
                 fence()
@@ -815,7 +890,12 @@ def main():
                         w.wait()
                 fence()
                 elapsed = time.perf_counter() - t0
-                if graphs is not None:
+                if final and keep_last:   # before anything else runs: the region's last step wrote these
+                    k = last_k if graphs is not None else args.steps - 1
+                    last[:] = [tau[(k // G) & 1][k % G].clone(), status.clone()]
+                if graphs is not None and not args.full:
+                    kernel_ms = None
+                elif graphs is not None:
                     # HIP events around an untimed replay (the NEXT K steps of the loop): K kernels back to back, so this average
                     # includes the kernel-to-kernel boundary (an upper bound of the pure kernel duration; the rocprofv3 summary
                     # under profiles/ has the exact figure)
@@ -832,11 +912,12 @@ def main():
             el = np.zeros(n)
             km = np.zeros(n)
             for r in range(n):
-                el[r], km[r] = sample()
-                # A sample takes two replays (the timed one, the one between HIP events): with an even number NG of regions the
-                # timed samples would visit every other region of the trajectory only -- and the one behind the jump back to tick 0
-                # three times in eleven.  One more untimed replay makes the stride 3: every region in turn (all ranks alike).
-                if graphs is not None and NG > 1 and NG % 2 == 0 and NG % 3 != 0:
+                el[r], km[r] = sample(r == n - 1)
+                # With --full a sample takes two replays (the timed one, the one between HIP events): with an even number NG of
+                # regions the timed samples would visit every other region of the trajectory only -- and the one behind the jump
+                # back to tick 0 three times in eleven.  One more untimed replay makes the stride 3: every region in turn (all
+                # ranks alike).  Without --full the stride is 1.
+                if args.full and graphs is not None and NG > 1 and NG % 2 == 0 and NG % 3 != 0:
                     replay()
                     fence()
             if collective:  # a sample lasts as long as its slowest rank
@@ -844,16 +925,16 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 el = t.cpu().numpy()
             pick = int(np.argsort(el)[n // 2])  # the median sample is the timed region reported
-            return dict(elapsed=float(el[pick]), kernel_ms=float(np.median(km)), samples_ms=[float(x * 1e3) for x in el],
-                        graph=graphs is not None, overlap=overlap)
+            return dict(elapsed=float(el[pick]), kernel_ms=None if np.isnan(km).any() else float(np.median(km)),
+                        samples_ms=[float(x * 1e3) for x in el], graph=graphs is not None, overlap=overlap, last=last)
 
         res = measure(with_gather)
         if peer is not None:
             peer.agree_no_failure()
-        if collective and args.steps > 0 and with_gather:
+        if args.full and collective and args.steps > 0 and with_gather:
             # the collected buffer holds every rank's torques in rank order: every rank sends a checksum of the block it computed
             # and checks every block it received against its sender's (peer copies: its own slot against its own buffer)
-            last = ((args.steps - 1) // G) & 1
+            last = ((last_k if res["graph"] else args.steps - 1) // G) & 1
             torch.cuda.synchronize()
             if peer is not None:
                 mine = peer.slot_equals(last, rank, tau[last])
@@ -870,38 +951,41 @@ def main():
         res["plain"] = measure(False) if (with_gather and second_without_gather) else None
         if peer is not None:
             peer.close()
-        # ---- what the loop saw, tick by tick (untimed): the K steps once more, eagerly, continuing the caller's loop where the
-        # last replay left it -- every tick's statuses, iteration counts and (warm) how many robots ended the tick with the
-        # working set they started it with
-        ok, it_mean, it_max, unchanged = True, [], 0, []
-        for k in range(T):
-            before = wset.clone() if warm else None
-            solve(k, tau[0][0], stream)
-            torch.cuda.synchronize()
-            ok = ok and bool((status == 0).all().item())
-            if placed or warm:
-                it = its[k & 1]
-                it_mean.append(float(it.float().mean().item()))
-                it_max = max(it_max, int(it.max().item()))
-            if warm:
-                unchanged.append(float((wset == before).float().mean().item()))
-        if collective:
-            okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
-            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-            ok = bool(okt.item())
-        res["ok"] = ok
         res["batch"], res["method"] = B, method
-        wrap, inside = [0], list(range(1, T)) or [0]                  # tick 0 follows the jump back from tick T - 1
         res["trajectory"] = {
             "states_per_replay": K, "ticks": T, "regions": NG, "dt": synth.CONTROL_PERIOD,
             "switched_per_tick": float(np.mean(switched[:-1])) if T > 1 else 0.0,   # robots whose support set changes, per tick
             "switched_at_wrap": float(switched[-1])}
+        if args.full:
+            # ---- what the loop saw, tick by tick (untimed): the K steps once more, eagerly, continuing the caller's loop where
+            # the last replay left it -- every tick's statuses, iteration counts and (warm) how many robots ended the tick with
+            # the working set they started it with
+            ok, it_mean, it_max, unchanged = True, [], 0, []
+            for k in range(T):
+                before = wset.clone() if warm else None
+                solve(k, tau[0][0], stream)
+                torch.cuda.synchronize()
+                ok = ok and bool((status == 0).all().item())
+                if placed or warm:
+                    it = its[k & 1]
+                    it_mean.append(float(it.float().mean().item()))
+                    it_max = max(it_max, int(it.max().item()))
+                if warm:
+                    unchanged.append(float((wset == before).float().mean().item()))
+            if collective:
+                okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
+                dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+                ok = bool(okt.item())
+            res["ok"] = ok
+            wrap, inside = [0], list(range(1, T)) or [0]                  # tick 0 follows the jump back from tick T - 1
+            if placed or warm:
+                res["iterations"] = {"mean": float(np.mean(it_mean)), "max": it_max}
+            if warm:
+                res["trajectory"]["working_set_unchanged"] = float(np.mean([unchanged[k] for k in inside]))
+                res["trajectory"]["working_set_unchanged_at_wrap"] = float(np.mean([unchanged[k] for k in wrap]))
         if placed or warm:
-            res["iterations"] = {"mean": float(np.mean(it_mean)), "max": it_max}
             res["trajectory"]["placement_give_ups"] = ctx.counter(capi.COUNTER_PLACEMENT_GIVE_UPS) - giveups0
         if warm:
-            res["trajectory"]["working_set_unchanged"] = float(np.mean([unchanged[k] for k in inside]))
-            res["trajectory"]["working_set_unchanged_at_wrap"] = float(np.mean([unchanged[k] for k in wrap]))
             # robots whose warm start was rejected and that were solved again cold inside the same launch (whole preset:
             # warm-up, settling and every timed replay included); with the fallback on none of them is ever reported
             res["trajectory"]["warm_rejected"] = ctx.counter(capi.COUNTER_WARM_RETRIES) - retries0
@@ -1159,13 +1243,16 @@ def main():
     others = [m for m in ("placed", "plain") if m != method] if method == "warm" else (["plain"] if method == "placed" else ["placed"])
     OTHER_KEY = {"placed": "cold_start", "plain": "unplaced", "warm": "warm_started"}
     few = min(args.replays, 5)
-    res = run_preset(args.gait, args.errors, gather, args.replays, world > 1, collect=args.collect, every=args.gather_every, method=method)
+    # a plain run times ONE region of exactly --steps steps; --full the median of --replays of them
+    res = run_preset(args.gait, args.errors, gather, args.replays if args.full else 1, world > 1 and args.full, collect=args.collect,
+                     every=args.gather_every, method=method, keep_last=bool(args.dump_outputs))
+    no_also = args.no_also or not args.full   # the other methods, layouts, presets and sizes: --full only
     # the same preset by the other methods (every rank takes part: the preset's consensus steps are collectives)
     beside = ({m: run_preset(args.gait, args.errors, False, few, False, method=m) for m in others}
-              if not (args.rpw or args.no_also) else {})
+              if not (args.rpw or no_also) else {})
     # ... and by the line's method on records instead of per-field arrays (the optional gather-friendly layout)
     on_records = (run_preset(args.gait, args.errors, False, few, False, method=method, records=True)
-                  if not (args.rpw or args.no_also or method == "plain" or collective) else None)
+                  if not (args.rpw or no_also or method == "plain" or collective) else None)
     # The other presets and every other BASELINE config, same process (one GPU only; fewer samples each):
     #   static-calm, trot at the headline batch; trot_b8192 (one rank's shard of configs[3]) and trot_b65536 (its global
     #   batch on one GPU), each by the line's method with the other methods beside it; pose_sqp_b4096 (configs[4]).
@@ -1182,7 +1269,7 @@ def main():
             e[OTHER_KEY[m]] = brief(run_preset(gait, errors, False, few, False, batch=bb, method=m))
         return e
 
-    if world == 1 and not collective and not args.no_also:
+    if world == 1 and not collective and not no_also:
         also = {}
         for gait, errors in (("static", "calm"), ("static", "survey"), ("trot", "survey")):
             if gait == args.gait and (gait == "trot" or errors == args.errors):
@@ -1203,7 +1290,7 @@ def main():
     # 8192 trot robots per GPU (configs[3]'s shard).  efficiency(N) = scale_point(N).value / (N * scale_point(1).without_gather)
     if args.gait == "trot" and B == SCALE_B:
         sp_res = res
-    elif args.no_also or (world == 1 and not collective):  # (one GPU: taken from also["trot_b8192"] below)
+    elif no_also or (world == 1 and not collective):  # (one GPU: taken from also["trot_b8192"] below)
         sp_res = None
     else:
         sp_res = run_preset("trot", "survey", gather, few, world > 1, collect=args.collect, every=args.gather_every,
@@ -1251,7 +1338,6 @@ def main():
     if rank == 0:
         elapsed = res["elapsed"]
         total = world * B * args.steps
-        roof, valu = roofline_of(res, args.gait, args.errors)
         line = {
             "metric": "control-step QP solves/sec (18-DoF, 4-contact) at 1/2/4/8 MI355X",
             "value": total / elapsed, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1273,7 +1359,6 @@ def main():
                                            "K steps (states_per_replay), consecutive regions continue the trajectory (`regions` captured "
                                            "graphs replayed in turn), so the jump back to tick 0 (switched_at_wrap; the steps after it run "
                                            "on hints a real loop never sees that stale) falls into one region in `regions`"),
-                       "iterations": res.get("iterations"),
                        "tracking_error": list(synth.tracking_error(args.gait, args.errors)),
                        "tracking_error_note": "half-widths of the uniform position (m) / rotation-vector (rad) / twist errors at tick 0: "
                                               "SURVEY.md 8(d)'s 0.02 / 0.05 / 0.1 unless --errors calm (static only; `also` "
@@ -1286,12 +1371,16 @@ def main():
                        "gather_stream": ("second captured stream" if res["overlap"] else "solve stream") if gather else None,
                        "gather_layout_ok": res.get("gather_layout_ok"),
                        "collect": args.collect if gather else None, "gather_every": args.gather_every if gather else None,
-                       "timed_region": "median of %d samples of exactly K steps, each between barrier + synchronize" % len(res["samples_ms"]),
+                       "timed_region": ("median of %d samples of exactly K steps, each between barrier + synchronize" % len(res["samples_ms"])
+                                        if len(res["samples_ms"]) > 1 else "one sample of exactly K steps between barrier + synchronize"),
+                       "timed_steps": len(res["samples_ms"]) * args.steps,
                        "settle_ms": args.settle_ms,
-                       "samples_ms": res["samples_ms"],
-                       "all_status_ok": res["ok"]},
-            "roofline": roof,
+                       "samples_ms": res["samples_ms"]},
         }
+        valu = None
+        if args.full:   # every tick's statuses and iteration counts, the kernel time of a replay of its own
+            line["config"].update(iterations=res.get("iterations"), all_status_ok=res["ok"])
+            line["roofline"], valu = roofline_of(res, args.gait, args.errors)
         if res["plain"] is not None:
             line["without_gather"] = {"value": total / res["plain"]["elapsed"], "ms_per_step": res["plain"]["elapsed"] / args.steps * 1e3,
                                       "samples_ms": res["plain"]["samples_ms"]}
@@ -1309,6 +1398,16 @@ def main():
             line["also"] = also
         if cpu is not None:
             line["cpu_baseline"] = cpu
+    if args.dump_outputs:   # the last timed step's efforts and statuses, every rank's robots in rank order
+        tau_last, status_last = res["last"]
+        if collective:
+            tau_all = torch.empty(world * B, 12, dtype=tau_last.dtype, device=dev)
+            status_all = torch.empty(world * B, dtype=status_last.dtype, device=dev)
+            dist.all_gather_into_tensor(tau_all, tau_last)
+            dist.all_gather_into_tensor(status_all, status_last)
+            tau_last, status_last = tau_all, status_all
+        if rank == 0:
+            write_outputs(args.dump_outputs, tau_last.cpu().numpy(), status_last.cpu().numpy())
 
     # The same steps with the other ways of collecting the results, so that a scaling run has something to compare the
     # per-step all-gather (the default: BASELINE's north star) with: one all-gather per 8 steps, and the peer-copy form.

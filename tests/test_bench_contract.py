@@ -1,13 +1,16 @@
 """The one-line JSON contract of bench.py: every key the driver reads, with the types and relations it relies on.
-CPU: the committed line of the last measured run (profiles/r6/bench_static_b4096.json).  GPU: short live runs."""
+CPU: the committed line of the last measured run (profiles/r6/bench_static_b4096.json).  GPU: short live runs, with --full
+(everything the line can carry) and without it (the headline figure alone, and the outputs of its last timed step)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
+from quadruped_locomotion_amd import synth
 
 TOP = {"metric": str, "value": float, "unit": str, "n_gpus": int, "steps": int, "warmup": int, "ms_per_step": float,
        "higher_is_better": bool, "scaling": str, "dtype": str, "data": str, "config": dict, "roofline": dict}
@@ -110,7 +113,7 @@ def test_committed_bench_line_follows_the_contract():
 @pytest.mark.gpu
 def test_live_bench_line_follows_the_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--cpu-seconds", "4",
-                          "--no-also"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-also", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "bench.py must print exactly one line"
@@ -137,26 +140,83 @@ def _bench(*argv, rc=0):
 def test_live_default_line_is_the_contract_workload_and_carries_the_other_presets():
     """`python bench.py` with no workload flags: BASELINE configs[1] on SURVEY.md 8(d)'s literal tracking errors, and an
     `also` object with static-calm and trot measured in the same process."""
-    d = check(_bench("--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--replays", "3"), want_cpu=False)
+    d = check(_bench("--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--replays", "3", "--full"), want_cpu=False)
     assert d["config"]["gait"] == "static" and d["config"]["tracking_error"] == [0.02, 0.05, 0.1]
     check_round6(d, 20)
     assert d["also"]["static-calm"]["kernel_ms"] < d["roofline"]["kernel_ms"]     # the calm preset is the lighter one
     # the plain entry as the method: the placed loop rides along instead; the placed loop: the plain entry does
-    d = check(_bench("--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--replays", "3", "--method", "plain", "--no-also"), want_cpu=False)
+    d = check(_bench("--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--replays", "3", "--method", "plain", "--no-also", "--full"),
+              want_cpu=False)
     assert d["config"]["method"] == "plain" and "cold_start" not in d
-    d = check(_bench("--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--replays", "3", "--method", "placed", "--ticks", "7"), want_cpu=False)
+    d = check(_bench("--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--replays", "3", "--method", "placed", "--ticks", "7", "--full"),
+              want_cpu=False)
     assert d["config"]["method"] == "placed" and d["unplaced"]["method"] == "plain" and d["unplaced"]["all_status_ok"] is True
     assert d["config"]["trajectory"]["ticks"] == 7 and d["config"]["states_per_replay"] == 20
 
 
 @pytest.mark.gpu
-def test_collective_path_with_one_rank():
+def test_plain_line_is_the_headline_alone_and_dumps_its_last_step(tmp_path, oracle):
+    """Without --full: exactly --steps timed steps (one region) and nothing measured beside them; --dump-outputs writes the
+    efforts and statuses of the last timed step.  K = 20 on the 200-tick trajectory: 10 regions, the timed one is the middle one
+    (region 5: ticks 100..119), so its last step solved tick 119.  K = 4500: one region, a chain of two 2000-step graphs and one
+    of 500 steps, whose last step solved tick 4499 % 200 = 99."""
+    for K, regions, tick in ((20, 10, 119), (4500, 1, 99)):
+        out = tmp_path / str(K)
+        d = json.loads(_bench("--steps", str(K), "--warmup", "3", "--dump-outputs", str(out)))
+        for k, t in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+            assert isinstance(d[k], t), k
+        assert d["metric"].startswith("control-step QP solves/sec") and d["unit"] == "solves/s" and d["dtype"] == "f64"
+        assert d["higher_is_better"] is True and d["steps"] == K and d["warmup"] == 3
+        assert d["config"]["timed_steps"] == K and len(d["config"]["samples_ms"]) == 1
+        assert abs(d["ms_per_step"] - d["config"]["samples_ms"][0] / K) < 1e-9 * d["ms_per_step"]
+        assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for k in ("also", "cpu_baseline", "roofline", "valu_issue", "cold_start", "unplaced", "records", "scale_point"):
+            assert k not in d, k
+        t = d["config"]["trajectory"]
+        assert d["config"]["method"] == "warm" and t["ticks"] == 200 and t["regions"] == regions and t["states_per_replay"] == K
+        tau, status = np.load(out / "tau.npy"), np.load(out / "status.npy")
+        assert tau.dtype == status.dtype == np.float64 and tau.shape == (4096, 12) and status.shape == (4096,)
+        t_ref, _, s_ref = oracle.balance_batch(synth.trajectory(4096, "static", 200, errors="survey")[tick], nthreads=8)
+        assert np.array_equal(status, s_ref) and (status == 0).all()
+        assert np.abs(tau - t_ref).max() < 1e-6                                  # BASELINE.json north_star
+
+
+def test_dump_writer_keeps_float64_and_samples_large_batches(tmp_path):
+    import bench
+    rng = np.random.default_rng(3)
+    tau, status = rng.normal(size=(100, 12)), np.zeros(100, np.int32)
+    bench.write_outputs(str(tmp_path / "small"), tau, status)
+    assert np.array_equal(np.load(tmp_path / "small" / "tau.npy"), tau) and not (tmp_path / "small" / "robot_index.npy").exists()
+    assert np.load(tmp_path / "small" / "status.npy").dtype == np.float64
+    B = bench.DUMP_MAX_ROBOTS + 1000
+    tau, status = rng.normal(size=(B, 12)), rng.integers(0, 3, B).astype(np.int32)
+    for name in ("a", "b"):
+        bench.write_outputs(str(tmp_path / name), tau, status)
+    rows = np.load(tmp_path / "a" / "robot_index.npy").astype(np.int64)
+    assert len(rows) == bench.DUMP_MAX_ROBOTS and (np.diff(rows) > 0).all()          # a sample without repeats, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "tau.npy"), tau[rows]) and np.array_equal(np.load(tmp_path / "a" / "status.npy"), status[rows])
+    for f in ("tau", "status", "robot_index"):                                      # the same seeded sample every run
+        assert np.array_equal(np.load(tmp_path / "a" / (f + ".npy")), np.load(tmp_path / "b" / (f + ".npy")))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "pose_sqp", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 2 and "balance workload" in out.stderr
+
+
+@pytest.mark.gpu
+def test_collective_path_with_one_rank(tmp_path, oracle):
     """The code path the N > 1 runs take -- RCCL process group, the K steps with their all-gathers captured into one
-    hipGraph, gathers on a second captured stream -- exercised with a single rank, then without the gather, then with
-    eager launches (what the ranks fall back to when a capture fails)."""
+    hipGraph, gathers on a second captured stream, the dumped outputs collected over the ranks -- exercised with a single
+    rank, then without the gather, then with eager launches (what the ranks fall back to when a capture fails)."""
     common = ("--force-collective", "--gait", "trot", "--batch", "8192", "--steps", "20", "--warmup", "3",
-              "--no-cpu-baseline", "--replays", "3")
-    d = check(_bench(*common, "--overlap-gather"), want_cpu=False)
+              "--no-cpu-baseline", "--replays", "3", "--full")
+    d = check(_bench(*common, "--overlap-gather", "--dump-outputs", str(tmp_path)), want_cpu=False)
+    # --full, K = 20 on 10 regions: a sample is three replays (timed, HIP events, one more), so the third timed sample is region
+    # 6 and its last step solved tick 6 K + K - 1 = 139
+    tau, status = np.load(tmp_path / "tau.npy"), np.load(tmp_path / "status.npy")
+    t_ref, _, s_ref = oracle.balance_batch(synth.trajectory(8192, "trot", 200, errors="survey")[139], nthreads=8)
+    assert tau.shape == (8192, 12) and np.array_equal(status, s_ref) and (status == 0).all()
+    assert np.abs(tau - t_ref).max() < 1e-6
     c = d["config"]
     assert c["rccl_ranks"] == 1 and d["n_gpus"] == 1 and c["robots_per_gpu"] == 8192 and c["all_status_ok"] is True
     assert c["launch"] == "hipGraph of K steps" and c["gather_stream"] == "second captured stream"
@@ -178,7 +238,7 @@ def test_collection_cadence_and_peer_copies_with_one_rank():
     """--gather-every K (one all-gather per K steps), --collect peer (copies into the ranks' buffers instead of a
     collective) and the `alternatives` object a several-rank line carries, each through the captured two-stream form."""
     common = ("--force-collective", "--overlap-gather", "--gait", "trot", "--batch", "8192", "--steps", "20", "--warmup", "3",
-              "--no-cpu-baseline", "--replays", "3")
+              "--no-cpu-baseline", "--replays", "3", "--full")
     d = check(_bench(*common, "--gather-every", "4"), want_cpu=False)
     c = d["config"]
     assert c["gather_every"] == 4 and c["collect"] == "rccl" and c["gather_layout_ok"] is True and c["all_status_ok"] is True

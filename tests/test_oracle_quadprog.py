@@ -1,8 +1,12 @@
 """Oracle pinning: the plain-C Goldfarb-Idnani restatement against the golden
-vectors produced by the reference's own compiled QuadProg++ (tests/tools/gen_goldens.py)
-and, where oracle/_ref was built, against that solver live."""
+vectors produced by the reference's own compiled QuadProg++ (tests/tools/gen_goldens.py,
+tests/tools/gen_quadprog_random.py) and, where oracle/_ref was built, against that solver live."""
+import os
+
 import numpy as np
 import pytest
+
+from conftest import ROOT
 
 
 @pytest.mark.parametrize("key,n,m", [("n12", 12, 20), ("n6", 6, 10)])
@@ -53,9 +57,8 @@ def test_error_paths(oracle):
     assert np.allclose(r["x"], [-1, 2, -3])
 
 
-def test_against_live_reference(oracle):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+def random_problems():
+    """300 seeded random QPs (G, g0, CE, CI, ci0); tests/tools/gen_quadprog_random.py recorded the reference's answers."""
     rng = np.random.default_rng(7)
     for _ in range(300):
         n, m, p = rng.integers(2, 13), rng.integers(0, 21), rng.integers(0, 2)
@@ -64,11 +67,30 @@ def test_against_live_reference(oracle):
         g0 = 10 * rng.normal(size=n)
         CI, ci0 = rng.normal(size=(n, m)), rng.normal(size=m) + 1.0
         CE = np.zeros((n, p)) if rng.random() < 0.5 else rng.normal(size=(n, p))
+        yield G, g0, CE, CI, ci0
+
+
+def input_sum(*arrays):
+    return float(sum(np.sum(a) for a in arrays))
+
+
+def test_against_live_reference(oracle):
+    """The reference's own compiled QuadProg++ on random problems: always against its answers as recorded in
+    tests/golden/quadprog_random.npz; the live comparison with the solver itself is an optional second half that runs only
+    where oracle/_ref was built (the reference tree is not on every machine)."""
+    rec = np.load(os.path.join(ROOT, "tests", "golden", "quadprog_random.npz"))
+    live = oracle.ref_lib() is not None
+    for k, (G, g0, CE, CI, ci0) in enumerate(random_problems()):
+        assert abs(input_sum(G, g0, CE, CI, ci0) - rec["input_sum"][k]) <= 1e-9 * max(1.0, abs(rec["input_sum"][k])), k
+        p = CE.shape[1]
         a = oracle.solve_quadprog(G, g0, CE, np.zeros(p), CI, ci0)
-        b = oracle.ref_solve_quadprog(G, g0, CE, np.zeros(p), CI, ci0)
-        assert a["status"] == b["status"]
-        if a["status"] == 0:
-            assert np.array_equal(a["x"], b["x"]) and a["f"] == b["f"]
+        refs = [dict(status=int(rec["status"][k]), x=rec["x"][k, :len(g0)], f=float(rec["f"][k]))]
+        if live:
+            refs.append(oracle.ref_solve_quadprog(G, g0, CE, np.zeros(p), CI, ci0))
+        for b in refs:
+            assert a["status"] == b["status"]
+            if a["status"] == 0:
+                assert np.array_equal(a["x"], b["x"]) and a["f"] == b["f"]
 
 
 def test_dummy_zero_equality_is_an_equality_along_the_first_column_of_G(oracle):

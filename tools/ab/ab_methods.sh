@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 reps=2; K=200
 while getopts "r:k:" o; do case $o in r) reps=$OPTARG;; k) K=$OPTARG;; esac; done
 shift $((OPTIND-1))
-run() { lib=$1; shift; python tools/experiments/bench_with_lib.py "$lib" --no-cpu-baseline --no-also --steps $K --warmup 10 "$@" 2>/dev/null | python -c "
+run() { lib=$1; shift; python tools/experiments/bench_with_lib.py "$lib" --full --no-cpu-baseline --no-also --steps $K --warmup 10 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); t=d['config']['trajectory']
 print('%7.2f (k %6.2f%s)' % (d['ms_per_step']*1e3, d['roofline']['kernel_ms']*1e3, ' same %.3f rej %d' % (t['working_set_unchanged'], t['warm_rejected']) if 'working_set_unchanged' in t else ''), end='')"; }

@@ -11,7 +11,7 @@ mkdir -p $OUT profiles/$R
 python3 tools/collect_profiles.py $OUT > $OUT/collect_profiles.log 2>&1
 rm -rf $OUT/raw
 cp $OUT/pmc_index.json profiles/$R/pmc_index.json
-b() { name=$1; shift; python3 bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; python3 bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 b static_b4096 --steps 200 --warmup 20
 # the driver's own arguments (K = 20, W = 5): what BENCH_rNN.json will hold
 b static_b4096_driver_args --steps 20 --warmup 5
