@@ -836,7 +836,6 @@ int qlamd_get_counter(qlamd_context *ctx, int counter, int64_t *value) {
 
 } // extern "C"
 
-// live: device pointer [B] or NULL (whole tick, QLAMD_MEM_DEVICE only): robots with 0 are left alone
 namespace {
 // qlamd_placement_from_iterations on device pointers (the caller holds the context's guard)
 // d_support: the robots' support flags ([B][4] bytes, device) or NULL -- the class of the sorted placement (place_key)
@@ -870,25 +869,6 @@ int launch_placement(qlamd_context *ctx, const int32_t *d_it, int64_t batch, int
 bool throughput_policy(int policy, int64_t batch) {
   return policy == QLAMD_PLACEMENT_THROUGHPUT || (policy == QLAMD_PLACEMENT_AUTO && batch >= QLAMD_THROUGHPUT_BATCH);
 }
-bool valid_policy(int policy) {
-  return policy == QLAMD_PLACEMENT_AUTO || policy == QLAMD_PLACEMENT_LATENCY || policy == QLAMD_PLACEMENT_THROUGHPUT ||
-         policy == QLAMD_PLACEMENT_NONE;
-}
-// What QLAMD_PLACEMENT_AUTO means for a call.  Without a warm start: the latency policy below QLAMD_THROUGHPUT_BATCH robots, the
-// throughput policy from there.  With one (measured on trajectories, profiles/r6/ab_warm_policies.txt: us per step of the loop,
-// latency / throughput / no placement): 4096 robots static 14.7 / 14.7 / 14.4, trot 19.9 / 19.7 / 19.6; 8192: 20.8 / 20.0 / 19.1
-// and 25.5 / 23.3 / 23.8; 12 288: 25.7 / 25.3 / 25.0 and 31.5 / 26.5 / 29.1 -- a warm-started launch lasts as long as its
-// slowest ROBOT (alone_probe.txt), so who shares a wavefront with whom no longer matters while every wavefront has a SIMD to
-// itself, and the latency policy, which starts the hard robots together, puts two slow wavefronts on one SIMD as soon as there
-// are two a SIMD: no placement up to QLAMD_WARM_UNPLACED_BATCH robots, the throughput policy (with its support classes) above.
-#ifndef QLAMD_WARM_UNPLACED_BATCH
-#define QLAMD_WARM_UNPLACED_BATCH 4096
-#endif
-int effective_policy(int policy, int64_t batch, bool warm) {
-  if (policy != QLAMD_PLACEMENT_AUTO) return policy;
-  if (warm) return batch <= QLAMD_WARM_UNPLACED_BATCH ? QLAMD_PLACEMENT_NONE : QLAMD_PLACEMENT_THROUGHPUT;
-  return batch >= QLAMD_THROUGHPUT_BATCH ? QLAMD_PLACEMENT_THROUGHPUT : QLAMD_PLACEMENT_LATENCY;
-}
 __global__ void identity_order_kernel(int32_t *order, int64_t B) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < B) order[i] = (int32_t)i;
@@ -896,158 +876,43 @@ __global__ void identity_order_kernel(int32_t *order, int64_t B) {
 } // namespace
 
 int qlamd::rt::placement_launch(qlamd_context *ctx, const int32_t *d_iterations, int64_t batch, int policy, int32_t *d_order,
-                                hipStream_t st) {
+                                hipStream_t st, const uint8_t *d_support) {
   if (policy == QLAMD_PLACEMENT_NONE) { // the batch order
     hipLaunchKernelGGL(identity_order_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, d_order, batch);
     return hipGetLastError() == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
   }
-  return launch_placement(ctx, d_iterations, batch, throughput_policy(policy, batch) ? 1 : 0, d_order, st);
+  return launch_placement(ctx, d_iterations, batch, throughput_policy(policy, batch) ? 1 : 0, d_order, st, d_support);
 }
 
-// pl: the placed entries' arrays (NULL otherwise), in the memory space of the call
-int qlamd::rt::balance_impl(qlamd_context *ctx, const qlamd_state_batch *in_user, const double *wrench, const uint8_t *live, int support_only,
-                            int64_t batch, double *joint_effort, double *contact_force, int32_t *status, int memory,
-                            void *stream, const qlamd_placement *pl) {
-  if (!ctx || !in_user || batch < 0 || !joint_effort || !status) return QLAMD_ERR_INVALID_ARGUMENT;
-  const int32_t *order = pl ? pl->robot_order : nullptr;
-  int32_t *iterations = pl ? pl->iterations : nullptr;
-  const int32_t *prev_iterations = pl ? pl->prev_iterations : nullptr;
-  int32_t *next_order = pl ? pl->next_robot_order : nullptr;
-  if ((prev_iterations != nullptr) != (next_order != nullptr)) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (next_order && !valid_policy(pl->policy)) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (next_order && (next_order == order || prev_iterations == iterations)) return QLAMD_ERR_INVALID_ARGUMENT; // read and written by one launch
-  const uint32_t *prev_ws = pl ? pl->prev_working_set : nullptr;
-  uint32_t *ws = pl ? pl->working_set : nullptr;
-  const bool warm = prev_ws || ws;
-  const int policy = next_order ? effective_policy(pl->policy, batch, warm) : QLAMD_PLACEMENT_NONE;
-  if (warm && memory != QLAMD_MEM_DEVICE) return QLAMD_ERR_INVALID_ARGUMENT; // (a host-buffer call is bound by its copies)
-  // (prev_ws == ws is fine: a robot's set is read and written by its own 16 lanes only -- updated in place)
-  const bool placed = order || iterations || next_order || warm;
-  // the one-lane kernels of qlamd_set_robots_per_wave know no placement (a lane is a robot there: nothing is shared)
-  if (placed && pick_rpw(ctx, batch) != 4) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (placed && batch > INT32_MAX) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (order && memory == QLAMD_MEM_HOST) {
-    // host memory can be checked: every robot exactly once
-    std::vector<uint8_t> seen((size_t)batch, 0);
-    for (int64_t k = 0; k < batch; k++) {
-      const int32_t o = order[k];
-      if (o < 0 || o >= batch || seen[(size_t)o]) return QLAMD_ERR_INVALID_ARGUMENT;
-      seen[(size_t)o] = 1;
-    }
-  }
-  qlamd_state_batch filled = *in_user;
-  const qlamd_state_batch *in = &filled;
-  if (!filled.joint_position || !filled.base_orientation || !filled.support_leg) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (wrench) {
-    // force distribution only: the base pose / twist fields are not read for arithmetic; point
-    // them at valid memory of sufficient size (joint_position is [B][12])
-    filled.base_position = filled.base_linear_velocity = filled.base_angular_velocity = filled.joint_position;
-    filled.desired_position = filled.desired_linear_velocity = filled.desired_angular_velocity = filled.joint_position;
-    filled.desired_orientation = filled.base_orientation;
-  } else if (!filled.base_position || !filled.base_linear_velocity || !filled.base_angular_velocity ||
-             !filled.desired_position || !filled.desired_orientation || !filled.desired_linear_velocity ||
-             !filled.desired_angular_velocity) {
-    return QLAMD_ERR_INVALID_ARGUMENT;
-  }
-  if (memory != QLAMD_MEM_DEVICE && memory != QLAMD_MEM_HOST) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (batch == 0) return QLAMD_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  QL_ENTER(ctx, st);
-  const size_t B = (size_t)batch;
-
-  StatePtrs s;
-  double *d_tau = joint_effort, *d_grf = contact_force;
-  int32_t *d_status = status;
-  bool small_host = false;
-  size_t out_off = 0, out_bytes = 0;
-  if (memory == QLAMD_MEM_HOST) {
-    // one staging slab: inputs then outputs, 256-byte aligned pieces
-    // (with an external wrench the pose / twist fields alias the head of joint_position)
-    const size_t rec = 24, qrec = 32;
-    const size_t sz[12] = {B * 96, B * rec, B * qrec, B * rec, B * rec, B * rec, B * qrec, B * rec, B * rec, B * 4,
-                           in->surface_normal ? B * 96 : 0, wrench ? B * 48 : 0};
-    const void *src[12] = {in->joint_position, in->base_position, in->base_orientation,
-                           in->base_linear_velocity, in->base_angular_velocity, in->desired_position,
-                           in->desired_orientation, in->desired_linear_velocity,
-                           in->desired_angular_velocity, in->support_leg, in->surface_normal, wrench};
-    size_t off[17], total = 0;
-    for (int k = 0; k < 12; k++) { off[k] = total; total += align256(sz[k]); }
-    off[15] = total; total += align256(order ? B * 4 : 0);
-    off[12] = total; total += align256(B * 96);
-    off[13] = total; total += align256(B * 96);
-    off[14] = total; total += align256(B * 4);
-    off[16] = total; total += align256(iterations ? B * 4 : 0);
-    int rc = ensure_ws(ctx, total);
-    if (rc != QLAMD_OK) return rc;
-    char *w = (char *)ctx->ws;
-    small_host = total <= kSmallHostCall && ensure_pinned(ctx, kSmallHostCall) == QLAMD_OK;
-    out_off = off[12];
-    out_bytes = total - off[12];
-    // QLAMD_ON_FAILURE_KEEP: a failed robot's entries are not written by the kernel, and the whole output region is
-    // copied back below -- so the caller's efforts / forces go up with the inputs and come back untouched
-    const bool keep = ctx->params.keep_on_failure != 0;
-    const size_t up_bytes = keep ? off[14] : off[12];
-    if (small_host) {
-      // a single robot or a few: a dozen separate pageable copies cost ~10 us each; pack, copy once
-      char *h = (char *)ctx->pinned;
-      for (int k = 0; k < 12; k++)
-        if (sz[k]) memcpy(h + off[k], src[k], sz[k]);
-      if (order) memcpy(h + off[15], order, B * 4);
-      if (keep) {
-        memcpy(h + off[12], joint_effort, B * 96);
-        if (contact_force) memcpy(h + off[13], contact_force, B * 96);
-      }
-      if (hipMemcpyAsync(w, h, up_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return QLAMD_ERR_HIP;
-    } else {
-      for (int k = 0; k < 12; k++)
-        if (sz[k] && hipMemcpyAsync(w + off[k], src[k], sz[k], hipMemcpyHostToDevice, st) != hipSuccess)
-          return QLAMD_ERR_HIP;
-      if (order && hipMemcpyAsync(w + off[15], order, B * 4, hipMemcpyHostToDevice, st) != hipSuccess) return QLAMD_ERR_HIP;
-      if (keep) {
-        if (hipMemcpyAsync(w + off[12], joint_effort, B * 96, hipMemcpyHostToDevice, st) != hipSuccess) return QLAMD_ERR_HIP;
-        if (contact_force && hipMemcpyAsync(w + off[13], contact_force, B * 96, hipMemcpyHostToDevice, st) != hipSuccess)
-          return QLAMD_ERR_HIP;
-      }
-    }
-    s = StatePtrs{(const double *)(w + off[0]), (const double *)(w + off[1]), (const double *)(w + off[2]),
-                  (const double *)(w + off[3]), (const double *)(w + off[4]), (const double *)(w + off[5]),
-                  (const double *)(w + off[6]), (const double *)(w + off[7]), (const double *)(w + off[8]),
-                  (const uint8_t *)(w + off[9]), in->surface_normal ? (const double *)(w + off[10]) : nullptr,
-                  wrench ? (const double *)(w + off[11]) : nullptr, nullptr, 0,
-                  order ? (const int32_t *)(w + off[15]) : nullptr, iterations ? (int32_t *)(w + off[16]) : nullptr,
-                  nullptr, nullptr, 0};
-    d_tau = (double *)(w + off[12]);
-    d_grf = contact_force ? (double *)(w + off[13]) : nullptr;
-    d_status = (int32_t *)(w + off[14]);
-  } else {
-    s = StatePtrs{in->joint_position, in->base_position, in->base_orientation, in->base_linear_velocity,
-                  in->base_angular_velocity, in->desired_position, in->desired_orientation,
-                  in->desired_linear_velocity, in->desired_angular_velocity, in->support_leg,
-                  in->surface_normal, wrench, live, support_only, order, iterations, nullptr, nullptr, 0};
-    // records instead of per-field arrays: the lane-cooperative kernels only (and never with an external wrench, whose entry
-    // points the unused pose fields at joint_position)
-    if (ctx->state_record_doubles && (pick_rpw(ctx, batch) != 4 || wrench)) return QLAMD_ERR_INVALID_ARGUMENT;
-    s.record_doubles = ctx->state_record_doubles;
-    s.prev_working_set = prev_ws;
-    s.working_set = ws;
-    s.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
-    // the next launch's placement: by extra wavefronts in front of this launch
-    const int chunk = batch >= QLAMD_THROUGHPUT_BATCH ? kShadowChunkLarge : (warm ? kShadowChunkWarm : kShadowChunkCold);
-    const int64_t shadows = (batch + chunk - 1) / chunk;
-    const bool three_wave_form = !in->surface_normal && batch >= (warm ? QLAMD_THREE_WAVE_WARM_BATCH : QLAMD_THROUGHPUT_BATCH);
-    if (next_order && policy == QLAMD_PLACEMENT_NONE) {
-      if (!three_wave_form) s.next_order = next_order; // (shadow_blocks stays 0: written by the slots themselves)
-    } else if (next_order && shadows <= kShadowMaxBlocks && pick_rpw(ctx, batch) == 4) {
-      s.prev_iterations = prev_iterations;
-      s.next_order = next_order;
-      s.place_throughput = policy == QLAMD_PLACEMENT_THROUGHPUT ? 1 : 0;
-      s.shadow_blocks = (int)shadows;
-      s.shadow_chunk = chunk;
-      s.place_hist = (uint32_t *)ctx->place_ws;
-      s.place_sync = (uint32_t *)ctx->place_sync;
-      s.place_wait = ctx->placement_wait;
-    }
+int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, int layout, const double *wrench, const uint8_t *live,
+                              int support_only, const qlamd_placement &pl, int64_t batch, double *d_tau, double *d_grf,
+                              int32_t *d_status, hipStream_t st) {
+  const bool warm = pl.prev_working_set || pl.working_set;
+  // (prev_working_set == working_set is fine: a robot's set is read and written by its own 16 lanes only -- updated in place)
+  const bool placed = pl.robot_order || pl.iterations || pl.next_robot_order || warm;
+  const int policy = pl.next_robot_order ? effective_policy(pl.policy, batch, warm) : QLAMD_PLACEMENT_NONE;
+  StatePtrs s{in.joint_position, in.base_position, in.base_orientation, in.base_linear_velocity, in.base_angular_velocity,
+              in.desired_position, in.desired_orientation, in.desired_linear_velocity, in.desired_angular_velocity,
+              in.support_leg, in.surface_normal, wrench, live, support_only, pl.robot_order, pl.iterations, nullptr, nullptr, 0};
+  s.record_doubles = layout == QLAMD_STATE_RECORDS ? QLAMD_STATE_RECORD_DOUBLES : 0;
+  s.prev_working_set = pl.prev_working_set;
+  s.working_set = pl.working_set;
+  s.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
+  // the next launch's placement: by extra wavefronts in front of this launch
+  const int chunk = batch >= QLAMD_THROUGHPUT_BATCH ? kShadowChunkLarge : (warm ? kShadowChunkWarm : kShadowChunkCold);
+  const int64_t shadows = (batch + chunk - 1) / chunk;
+  const bool three_wave_form = !in.surface_normal && batch >= (warm ? QLAMD_THREE_WAVE_WARM_BATCH : QLAMD_THROUGHPUT_BATCH);
+  if (pl.next_robot_order && policy == QLAMD_PLACEMENT_NONE) {
+    if (!three_wave_form) s.next_order = pl.next_robot_order; // (shadow_blocks stays 0: written by the slots themselves)
+  } else if (pl.next_robot_order && shadows <= kShadowMaxBlocks && pick_rpw(ctx, batch) == 4) {
+    s.prev_iterations = pl.prev_iterations;
+    s.next_order = pl.next_robot_order;
+    s.place_throughput = policy == QLAMD_PLACEMENT_THROUGHPUT ? 1 : 0;
+    s.shadow_blocks = (int)shadows;
+    s.shadow_chunk = chunk;
+    s.place_hist = (uint32_t *)ctx->place_ws;
+    s.place_sync = (uint32_t *)ctx->place_sync;
+    s.place_wait = ctx->placement_wait;
   }
 
   hipError_t e;
@@ -1077,42 +942,113 @@ int qlamd::rt::balance_impl(qlamd_context *ctx, const qlamd_state_batch *in_user
     default: e = launch_balance<64>(ctx, s, batch, d_tau, d_grf, d_status, st); break;
   }
   if (e != hipSuccess) return QLAMD_ERR_HIP;
-  if (next_order && memory == QLAMD_MEM_DEVICE && policy == QLAMD_PLACEMENT_NONE && !s.next_order) {
-    hipLaunchKernelGGL(identity_order_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, next_order, batch);
-    if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  }
-  if (next_order && memory == QLAMD_MEM_DEVICE && !s.shadow_blocks && policy != QLAMD_PLACEMENT_NONE) { // more robots than the shadow wavefronts take: launches of their own
-    const int rc = launch_placement(ctx, prev_iterations, batch, policy == QLAMD_PLACEMENT_THROUGHPUT ? 1 : 0, next_order, st, s.stance);
-    if (rc != QLAMD_OK) return rc;
-  }
-
-  if (memory == QLAMD_MEM_HOST && small_host) {
-    char *h = (char *)ctx->pinned, *w = (char *)ctx->ws;
-    if (hipMemcpyAsync(h + out_off, w + out_off, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return QLAMD_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return QLAMD_ERR_HIP;
-    memcpy(joint_effort, h + ((char *)d_tau - w), B * 96);
-    if (contact_force) memcpy(contact_force, h + ((char *)d_grf - w), B * 96);
-    memcpy(status, h + ((char *)d_status - w), B * 4);
-    if (iterations) memcpy(iterations, h + ((char *)s.iterations - w), B * 4);
-  } else if (memory == QLAMD_MEM_HOST) {
-    if (hipMemcpyAsync(joint_effort, d_tau, B * 96, hipMemcpyDeviceToHost, st) != hipSuccess) return QLAMD_ERR_HIP;
-    if (contact_force &&
-        hipMemcpyAsync(contact_force, d_grf, B * 96, hipMemcpyDeviceToHost, st) != hipSuccess)
-      return QLAMD_ERR_HIP;
-    if (hipMemcpyAsync(status, d_status, B * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return QLAMD_ERR_HIP;
-    if (iterations && hipMemcpyAsync(iterations, s.iterations, B * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return QLAMD_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return QLAMD_ERR_HIP;
-  }
-  if (next_order && memory == QLAMD_MEM_HOST)
-    return qlamd_placement_from_iterations(ctx, prev_iterations, batch, policy, next_order, QLAMD_MEM_HOST, stream);
+  // a next placement the launch did not make itself (QLAMD_PLACEMENT_NONE in the three-wavefront form, more robots than the
+  // shadow wavefronts take): launches of their own
+  if (pl.next_robot_order && !s.next_order)
+    return placement_launch(ctx, pl.prev_iterations, batch, policy, pl.next_robot_order, st, s.stance);
   return QLAMD_OK;
 }
+
+namespace {
+// The four public balance / force-distribution entries: the checks of their arguments, the host buffers' staging, then
+// balance_launch.  pl: the placed entries' placement (NULL otherwise), in the memory space of the call
+int balance_entry(qlamd_context *ctx, const qlamd_state_batch *in_user, const double *wrench, int64_t batch, const qlamd_placement *pl,
+                  double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream) {
+  if (!ctx || !in_user || batch < 0 || !joint_effort || !status) return QLAMD_ERR_INVALID_ARGUMENT;
+  qlamd_placement p;
+  memset(&p, 0, sizeof(p));
+  if (pl) p = *pl;
+  if (!placement_ok(p)) return QLAMD_ERR_INVALID_ARGUMENT;
+  const bool warm = p.prev_working_set || p.working_set;
+  if (warm && memory != QLAMD_MEM_DEVICE) return QLAMD_ERR_INVALID_ARGUMENT; // (a host-buffer call is bound by its copies)
+  const bool placed = p.robot_order || p.iterations || p.next_robot_order || warm;
+  // the one-lane kernels of qlamd_set_robots_per_wave know no placement (a lane is a robot there: nothing is shared)
+  if (placed && pick_rpw(ctx, batch) != 4) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (placed && batch > INT32_MAX) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (p.robot_order && memory == QLAMD_MEM_HOST) {
+    // host memory can be checked: every robot exactly once
+    std::vector<uint8_t> seen((size_t)batch, 0);
+    for (int64_t k = 0; k < batch; k++) {
+      const int32_t o = p.robot_order[k];
+      if (o < 0 || o >= batch || seen[(size_t)o]) return QLAMD_ERR_INVALID_ARGUMENT;
+      seen[(size_t)o] = 1;
+    }
+  }
+  qlamd_state_batch in = *in_user;
+  if (!in.joint_position || !in.base_orientation || !in.support_leg) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (wrench) {
+    // force distribution only: the base pose / twist fields are not read for arithmetic; point
+    // them at valid memory of sufficient size (joint_position is [B][12])
+    in.base_position = in.base_linear_velocity = in.base_angular_velocity = in.joint_position;
+    in.desired_position = in.desired_linear_velocity = in.desired_angular_velocity = in.joint_position;
+    in.desired_orientation = in.base_orientation;
+  } else if (!in.base_position || !in.base_linear_velocity || !in.base_angular_velocity || !in.desired_position ||
+             !in.desired_orientation || !in.desired_linear_velocity || !in.desired_angular_velocity) {
+    return QLAMD_ERR_INVALID_ARGUMENT;
+  }
+  if (memory != QLAMD_MEM_DEVICE && memory != QLAMD_MEM_HOST) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (batch == 0) return QLAMD_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
+  hipStream_t st = (hipStream_t)stream;
+  QL_ENTER(ctx, st);
+  if (memory == QLAMD_MEM_DEVICE) {
+    // records instead of per-field arrays: the lane-cooperative kernels only (and never with an external wrench, whose entry
+    // points the unused pose fields at joint_position); host-buffer calls take per-field arrays whatever the option says
+    const int layout = ctx->state_record_doubles ? QLAMD_STATE_RECORDS : QLAMD_STATE_FIELDS;
+    if (layout == QLAMD_STATE_RECORDS && (pick_rpw(ctx, batch) != 4 || wrench)) return QLAMD_ERR_INVALID_ARGUMENT;
+    return balance_launch(ctx, in, layout, wrench, nullptr, 0, p, batch, joint_effort, contact_force, status, st);
+  }
+  // host buffers: inputs, then outputs.  QLAMD_ON_FAILURE_KEEP: a failed robot's entries are not written by the kernel, and
+  // the outputs are copied back whole -- so the caller's efforts / forces go up with the inputs and come back untouched.
+  // (with an external wrench the pose / twist fields alias the head of joint_position)
+  const size_t B = (size_t)batch;
+  const bool keep = ctx->params.keep_on_failure != 0;
+  Staged sg;
+  const int i_q = sg.add(in.joint_position, B * 96, true, false), i_pos = sg.add(in.base_position, B * 24, true, false);
+  const int i_quat = sg.add(in.base_orientation, B * 32, true, false), i_lin = sg.add(in.base_linear_velocity, B * 24, true, false);
+  const int i_ang = sg.add(in.base_angular_velocity, B * 24, true, false), i_dpos = sg.add(in.desired_position, B * 24, true, false);
+  const int i_dquat = sg.add(in.desired_orientation, B * 32, true, false);
+  const int i_dlin = sg.add(in.desired_linear_velocity, B * 24, true, false);
+  const int i_dang = sg.add(in.desired_angular_velocity, B * 24, true, false), i_sup = sg.add(in.support_leg, B * 4, true, false);
+  const int i_nrm = sg.add(in.surface_normal, B * 96, true, false), i_w = sg.add(wrench, B * 48, true, false);
+  const int i_ord = sg.add(p.robot_order, B * 4, true, false);
+  const int o_tau = sg.add(joint_effort, B * 96, keep, true), o_grf = sg.add(contact_force, B * 96, keep, true);
+  const int o_st = sg.add(status, B * 4, false, true), o_it = sg.add(p.iterations, B * 4, false, true);
+  int rc = sg.upload(ctx, st);
+  if (rc != QLAMD_OK) return rc;
+  const qlamd_state_batch d{sg.dev<const double>(i_q), sg.dev<const double>(i_pos), sg.dev<const double>(i_quat),
+                            sg.dev<const double>(i_lin), sg.dev<const double>(i_ang), sg.dev<const double>(i_dpos),
+                            sg.dev<const double>(i_dquat), sg.dev<const double>(i_dlin), sg.dev<const double>(i_dang),
+                            sg.dev<const uint8_t>(i_sup), sg.dev<const double>(i_nrm)};
+  qlamd_placement dp;
+  memset(&dp, 0, sizeof(dp));
+  dp.robot_order = sg.dev<const int32_t>(i_ord);
+  dp.iterations = sg.dev<int32_t>(o_it);
+  rc = balance_launch(ctx, d, QLAMD_STATE_FIELDS, sg.dev<const double>(i_w), nullptr, 0, dp, batch, sg.dev<double>(o_tau),
+                      sg.dev<double>(o_grf), sg.dev<int32_t>(o_st), st);
+  if (rc == QLAMD_OK) rc = sg.finish(st);
+  if (rc == QLAMD_OK && p.next_robot_order)
+    rc = qlamd_placement_from_iterations(ctx, p.prev_iterations, batch, p.policy, p.next_robot_order, QLAMD_MEM_HOST, stream);
+  return rc;
+}
+// the force-distribution entries' state: the four arrays they read
+qlamd_state_batch wrench_state(const double *joint_position, const double *base_orientation, const uint8_t *support_leg,
+                               const double *surface_normal) {
+  qlamd_state_batch in;
+  memset(&in, 0, sizeof(in));
+  in.joint_position = joint_position;
+  in.base_orientation = base_orientation;
+  in.support_leg = support_leg;
+  in.surface_normal = surface_normal;
+  return in;
+}
+} // namespace
 
 extern "C" {
 
 int qlamd_balance_solve_batch(qlamd_context *ctx, const qlamd_state_batch *in, int64_t batch, double *joint_effort,
                               double *contact_force, int32_t *status, int memory, void *stream) {
-  return balance_impl(ctx, in, nullptr, nullptr, 0, batch, joint_effort, contact_force, status, memory, stream);
+  return balance_entry(ctx, in, nullptr, batch, nullptr, joint_effort, contact_force, status, memory, stream);
 }
 
 int qlamd_force_distribution_batch(qlamd_context *ctx, const double *joint_position, const double *base_orientation,
@@ -1120,18 +1056,13 @@ int qlamd_force_distribution_batch(qlamd_context *ctx, const double *joint_posit
                                    const double *virtual_wrench, int64_t batch, double *joint_effort,
                                    double *contact_force, int32_t *status, int memory, void *stream) {
   if (!virtual_wrench) return QLAMD_ERR_INVALID_ARGUMENT;
-  qlamd_state_batch in;
-  memset(&in, 0, sizeof(in));
-  in.joint_position = joint_position;
-  in.base_orientation = base_orientation;
-  in.support_leg = support_leg;
-  in.surface_normal = surface_normal;
-  return balance_impl(ctx, &in, virtual_wrench, nullptr, 0, batch, joint_effort, contact_force, status, memory, stream);
+  const qlamd_state_batch in = wrench_state(joint_position, base_orientation, support_leg, surface_normal);
+  return balance_entry(ctx, &in, virtual_wrench, batch, nullptr, joint_effort, contact_force, status, memory, stream);
 }
 
 int qlamd_balance_solve_placed_batch(qlamd_context *ctx, const qlamd_state_batch *in, int64_t batch, const qlamd_placement *placement,
                                      double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream) {
-  return balance_impl(ctx, in, nullptr, nullptr, 0, batch, joint_effort, contact_force, status, memory, stream, placement);
+  return balance_entry(ctx, in, nullptr, batch, placement, joint_effort, contact_force, status, memory, stream);
 }
 
 int qlamd_force_distribution_placed_batch(qlamd_context *ctx, const double *joint_position, const double *base_orientation,
@@ -1139,13 +1070,8 @@ int qlamd_force_distribution_placed_batch(qlamd_context *ctx, const double *join
                                           const double *virtual_wrench, int64_t batch, const qlamd_placement *placement,
                                           double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream) {
   if (!virtual_wrench) return QLAMD_ERR_INVALID_ARGUMENT;
-  qlamd_state_batch in;
-  memset(&in, 0, sizeof(in));
-  in.joint_position = joint_position;
-  in.base_orientation = base_orientation;
-  in.support_leg = support_leg;
-  in.surface_normal = surface_normal;
-  return balance_impl(ctx, &in, virtual_wrench, nullptr, 0, batch, joint_effort, contact_force, status, memory, stream, placement);
+  const qlamd_state_batch in = wrench_state(joint_position, base_orientation, support_leg, surface_normal);
+  return balance_entry(ctx, &in, virtual_wrench, batch, placement, joint_effort, contact_force, status, memory, stream);
 }
 
 int qlamd_place_next_call(qlamd_context *ctx, const qlamd_placement *placement) {
@@ -1153,10 +1079,7 @@ int qlamd_place_next_call(qlamd_context *ctx, const qlamd_placement *placement) 
   QL_ENTER_NO_STREAM(ctx);
   ctx->has_next_placement = false;
   if (!placement) return QLAMD_OK;
-  if ((placement->prev_iterations != nullptr) != (placement->next_robot_order != nullptr)) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (placement->next_robot_order && !valid_policy(placement->policy)) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (placement->next_robot_order && (placement->next_robot_order == placement->robot_order || placement->prev_iterations == placement->iterations))
-    return QLAMD_ERR_INVALID_ARGUMENT;
+  if (!placement_ok(*placement)) return QLAMD_ERR_INVALID_ARGUMENT;
   ctx->next_placement = *placement;
   ctx->has_next_placement = true;
   return QLAMD_OK;
@@ -1175,8 +1098,7 @@ int qlamd_placement_from_iterations(qlamd_context *ctx, const int32_t *iteration
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
     QL_ENTER(ctx, (hipStream_t)stream);
-    hipLaunchKernelGGL(identity_order_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, robot_order, batch);
-    return hipGetLastError() == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
+    return placement_launch(ctx, nullptr, batch, QLAMD_PLACEMENT_NONE, robot_order, (hipStream_t)stream);
   }
   if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
   hipStream_t st = (hipStream_t)stream;

@@ -184,8 +184,6 @@ struct CallGuard {
   ::qlamd::rt::CallGuard ql_guard_((ctx), nullptr, false); \
   if (ql_guard_.rc != QLAMD_OK) return ql_guard_.rc
 
-// balance_kernel.hip: the control step behind qlamd_balance_solve_batch / qlamd_force_distribution_batch, with the
-// whole tick's per-robot `live` flags (device pointer or NULL)
 // Robots per wavefront of the balance kernel.  The lane-cooperative kernel (4) wins at every batch size measured
 // (1 K ... 1 M robots, static and trot: tools/batch_sweep.py); the one-lane-per-robot kernels stay selectable as an
 // independent second implementation (different QP linear algebra) for cross-checks.
@@ -193,12 +191,47 @@ inline int pick_rpw(const qlamd_context *ctx, int64_t batch) {
   (void)batch;
   return ctx->rpw_override ? ctx->rpw_override : 4;
 }
-int balance_impl(qlamd_context *ctx, const qlamd_state_batch *in_user, const double *wrench, const uint8_t *live, int support_only,
-                 int64_t batch, double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream,
-                 const qlamd_placement *pl = nullptr);
+// balance_kernel.hip: one balance launch on device arrays, for callers that hold the context's guard and have checked their
+// arguments -- the public balance / force-distribution entries and the whole tick.  layout: QLAMD_STATE_FIELDS or
+// QLAMD_STATE_RECORDS (lane-cooperative kernels, no wrench); live: the whole tick's per-robot flags or NULL; pl: a checked
+// placement (all NULL: none), its arrays on the device, next_robot_order made behind the launch.
+int balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, int layout, const double *wrench, const uint8_t *live,
+                   int support_only, const qlamd_placement &pl, int64_t batch, double *joint_effort, double *contact_force,
+                   int32_t *status, hipStream_t st);
 
-// qlamd_placement_from_iterations on device pointers, for entries that hold the context's guard already (balance_kernel.hip)
-int placement_launch(qlamd_context *ctx, const int32_t *d_iterations, int64_t batch, int policy, int32_t *d_order, hipStream_t st);
+#ifndef QLAMD_THROUGHPUT_BATCH
+#define QLAMD_THROUGHPUT_BATCH 16384 // robots from which the three-wavefront form of the balance kernel runs
+#endif
+inline bool valid_policy(int policy) {
+  return policy == QLAMD_PLACEMENT_AUTO || policy == QLAMD_PLACEMENT_LATENCY || policy == QLAMD_PLACEMENT_THROUGHPUT ||
+         policy == QLAMD_PLACEMENT_NONE;
+}
+// The checks on a qlamd_placement (qlamd_place_next_call, the placed balance entries): prev_iterations and next_robot_order
+// come together, and an array is never read and written by one launch
+inline bool placement_ok(const qlamd_placement &pl) {
+  if (!pl.next_robot_order) return !pl.prev_iterations;
+  return pl.prev_iterations && valid_policy(pl.policy) && pl.next_robot_order != pl.robot_order && pl.prev_iterations != pl.iterations;
+}
+// What QLAMD_PLACEMENT_AUTO means for a call.  Without a warm start: the latency policy below QLAMD_THROUGHPUT_BATCH robots, the
+// throughput policy from there.  With one (measured on trajectories, profiles/r6/ab_warm_policies.txt: us per step of the loop,
+// latency / throughput / no placement): 4096 robots static 14.7 / 14.7 / 14.4, trot 19.9 / 19.7 / 19.6; 8192: 20.8 / 20.0 / 19.1
+// and 25.5 / 23.3 / 23.8; 12 288: 25.7 / 25.3 / 25.0 and 31.5 / 26.5 / 29.1 -- a warm-started launch lasts as long as its
+// slowest ROBOT (alone_probe.txt), so who shares a wavefront with whom no longer matters while every wavefront has a SIMD to
+// itself, and the latency policy, which starts the hard robots together, puts two slow wavefronts on one SIMD as soon as there
+// are two a SIMD: no placement up to QLAMD_WARM_UNPLACED_BATCH robots, the throughput policy (with its support classes) above.
+#ifndef QLAMD_WARM_UNPLACED_BATCH
+#define QLAMD_WARM_UNPLACED_BATCH 4096
+#endif
+inline int effective_policy(int policy, int64_t batch, bool warm) {
+  if (policy != QLAMD_PLACEMENT_AUTO) return policy;
+  if (warm) return batch <= QLAMD_WARM_UNPLACED_BATCH ? QLAMD_PLACEMENT_NONE : QLAMD_PLACEMENT_THROUGHPUT;
+  return batch >= QLAMD_THROUGHPUT_BATCH ? QLAMD_PLACEMENT_THROUGHPUT : QLAMD_PLACEMENT_LATENCY;
+}
+
+// qlamd_placement_from_iterations on device pointers, for entries that hold the context's guard already (balance_kernel.hip);
+// d_support: the robots' support flags ([B][4] bytes, device) or NULL -- the class of the throughput placement
+int placement_launch(qlamd_context *ctx, const int32_t *d_iterations, int64_t batch, int policy, int32_t *d_order, hipStream_t st,
+                     const uint8_t *d_support = nullptr);
 
 // The placement a lane-cooperative QP kernel runs in (qlamd_place_next_call): which problem sits in which slot of the
 // launch, and where the iteration counts go.  Both NULL = slot s takes problem s.
@@ -243,12 +276,11 @@ inline int take_placement(qlamd_context *ctx, int memory, int64_t batch, PlacePt
   pp->prev_working_set = reinterpret_cast<const unsigned long long *>(pl.prev_working_set);
   pp->working_set = reinterpret_cast<unsigned long long *>(pl.working_set);
   *next = pl;
-  // QLAMD_PLACEMENT_AUTO with a warm start (the whole-body step): no placement up to 4096 problems, the throughput policy above --
-  // include/qlamd.h; with no placement the solving launch writes the identity itself and nothing is launched behind it (the
-  // placement's two launches were 5 of the 23 us of a warm-started whole-body step of 4096 robots)
-  if (pl.next_robot_order && pl.policy == QLAMD_PLACEMENT_AUTO && (pl.prev_working_set || pl.working_set))
-    next->policy = batch <= 4096 ? QLAMD_PLACEMENT_NONE : QLAMD_PLACEMENT_THROUGHPUT;
-  if (pl.next_robot_order && next->policy == QLAMD_PLACEMENT_NONE && (pl.prev_working_set || pl.working_set)) {
+  // with a warm start (the whole-body step) and no placement the solving launch writes the identity itself and nothing is
+  // launched behind it (the placement's two launches were 5 of the 23 us of a warm-started whole-body step of 4096 robots)
+  const bool warm = pl.prev_working_set || pl.working_set;
+  if (pl.next_robot_order && warm) next->policy = effective_policy(pl.policy, batch, true);
+  if (pl.next_robot_order && next->policy == QLAMD_PLACEMENT_NONE && warm) {
     pp->identity_out = pl.next_robot_order;
     next->next_robot_order = nullptr;
   }
@@ -288,11 +320,14 @@ constexpr size_t kSmallHostCall = 256 * 1024; // below this a host-buffer call g
 // one copy down (the span of the outputs) instead of one pageable copy per array.
 struct Staged {
   struct Item { void *host; size_t bytes; bool in, out; size_t off; };
-  Item items[24];
+  static constexpr int kMaxItems = 24;
+  Item items[kMaxItems];
   int n = 0;
+  bool full = false;    // more than kMaxItems arrays were added (upload() refuses the call)
   char *base = nullptr;
   char *slab = nullptr; // pinned mirror of the workspace for small calls
   int add(const void *host, size_t bytes, bool in, bool out) {
+    if (n == kMaxItems) { full = true; return n - 1; }
     items[n] = Item{const_cast<void *>(host), host ? bytes : 0, in, out, 0};
     return n++;
   }
@@ -305,6 +340,7 @@ struct Staged {
     }
   }
   int upload(qlamd_context *ctx, hipStream_t st) {
+    if (full) return QLAMD_ERR_INVALID_ARGUMENT;
     size_t total = 0;
     for (int k = 0; k < n; k++) { items[k].off = total; total += align256(items[k].bytes); }
     int rc = ensure_ws(ctx, total ? total : 256);

@@ -483,35 +483,23 @@ static int pose_impl(const PoseCall &call, qlamd_context *ctx, const qlamd_pose_
   int32_t *d_it = call.iterations, *d_st = call.status, *d_stage = call.stage;
   const double *d_min = call.min_len, *d_sfo = call.sfo;
   uint8_t *d_ok = call.ok;
+  Staged sg;
   if (memory == QLAMD_MEM_HOST) {
-    enum { kIn = 10 };
-    const size_t sz[kIn] = {B * 96, B * 96, B * 64, in->center_of_mass ? B * 24 : 0, B * 32, in->pose ? B * 56 : 0,
-                            in->stance_mask ? B * 4 : 0, in->n_vertices ? B * 4 : 0, call.min_len ? B * 32 : 0,
-                            call.sfo ? B * 96 : 0};
-    const void *src[kIn] = {in->stance, in->nominal_stance, in->support_polygon, in->center_of_mass,
-                            in->max_limb_length, in->pose, in->stance_mask, in->n_vertices, call.min_len, call.sfo};
-    size_t off[kIn + 5], total = 0;
-    for (int k = 0; k < kIn; k++) { off[k] = total; total += align256(sz[k]); }
-    const size_t osz[5] = {B * 56, B * 4, B * 4, B * 4, B};
-    for (int k = 0; k < 5; k++) { off[kIn + k] = total; total += align256(osz[k]); }
-    int rc = ensure_ws(ctx, total);
+    const int i_st = sg.add(in->stance, B * 96, true, false), i_nom = sg.add(in->nominal_stance, B * 96, true, false);
+    const int i_poly = sg.add(in->support_polygon, B * 64, true, false), i_com = sg.add(in->center_of_mass, B * 24, true, false);
+    const int i_len = sg.add(in->max_limb_length, B * 32, true, false), i_pose = sg.add(in->pose, B * 56, true, false);
+    const int i_mask = sg.add(in->stance_mask, B * 4, true, false), i_nv = sg.add(in->n_vertices, B * 4, true, false);
+    const int i_min = sg.add(call.min_len, B * 32, true, false), i_sfo = sg.add(call.sfo, B * 96, true, false);
+    const int o_out = sg.add(call.pose_out, B * 56, false, true), o_it = sg.add(call.iterations, B * 4, false, true);
+    const int o_st = sg.add(call.status, B * 4, false, true), o_stage = sg.add(call.stage, B * 4, false, true);
+    const int o_ok = sg.add(call.ok, B, false, true);
+    const int rc = sg.upload(ctx, st);
     if (rc != QLAMD_OK) return rc;
-    char *w = (char *)ctx->ws;
-    for (int k = 0; k < kIn; k++)
-      if (sz[k] && hipMemcpyAsync(w + off[k], src[k], sz[k], hipMemcpyHostToDevice, st) != hipSuccess)
-        return QLAMD_ERR_HIP;
-    s = PosePtrs{(const double *)(w + off[0]), (const double *)(w + off[1]), (const double *)(w + off[2]),
-                 in->center_of_mass ? (const double *)(w + off[3]) : nullptr, (const double *)(w + off[4]),
-                 in->pose ? (const double *)(w + off[5]) : nullptr,
-                 in->stance_mask ? (const uint8_t *)(w + off[6]) : nullptr,
-                 in->n_vertices ? (const int32_t *)(w + off[7]) : nullptr};
-    d_min = call.min_len ? (const double *)(w + off[8]) : nullptr;
-    d_sfo = call.sfo ? (const double *)(w + off[9]) : nullptr;
-    d_out = (double *)(w + off[kIn]);
-    d_it = (int32_t *)(w + off[kIn + 1]);
-    d_st = (int32_t *)(w + off[kIn + 2]);
-    d_stage = (int32_t *)(w + off[kIn + 3]);
-    d_ok = (uint8_t *)(w + off[kIn + 4]);
+    s = PosePtrs{sg.dev<const double>(i_st), sg.dev<const double>(i_nom), sg.dev<const double>(i_poly), sg.dev<const double>(i_com),
+                 sg.dev<const double>(i_len), sg.dev<const double>(i_pose), sg.dev<const uint8_t>(i_mask), sg.dev<const int32_t>(i_nv)};
+    d_min = sg.dev<const double>(i_min); d_sfo = sg.dev<const double>(i_sfo);
+    d_out = sg.dev<double>(o_out); d_it = sg.dev<int32_t>(o_it); d_st = sg.dev<int32_t>(o_st); d_stage = sg.dev<int32_t>(o_stage);
+    d_ok = sg.dev<uint8_t>(o_ok);
   }
   const unsigned rgrid = (unsigned)((batch + coop::kPoseCoopRows - 1) / coop::kPoseCoopRows); // 4 problems per wavefront
   switch (mode) {
@@ -534,19 +522,7 @@ static int pose_impl(const PoseCall &call, qlamd_context *ctx, const qlamd_pose_
       break;
   }
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  if (memory == QLAMD_MEM_HOST) {
-    const auto back = [&](void *dst, const void *srcp, size_t n) {
-      return !dst || hipMemcpyAsync(dst, srcp, n, hipMemcpyDeviceToHost, st) == hipSuccess;
-    };
-    bool fine = true;
-    if (mode != kPoseCheck) fine = fine && back(call.pose_out, d_out, B * 56);
-    if (mode == kPoseSqp || mode == kPoseBaseAuto) fine = fine && back(call.iterations, d_it, B * 4);
-    if (has_status) fine = fine && back(call.status, d_st, B * 4);
-    if (mode == kPoseBaseAuto) fine = fine && back(call.stage, d_stage, B * 4);
-    if (mode == kPoseCheck) fine = fine && back(call.ok, d_ok, B);
-    if (!fine || hipStreamSynchronize(st) != hipSuccess) return QLAMD_ERR_HIP;
-  }
-  return QLAMD_OK;
+  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
 }
 
 int qlamd_pose_sqp_batch(qlamd_context *ctx, const qlamd_pose_params *params, const qlamd_pose_batch *in,
@@ -610,23 +586,17 @@ int qlamd_qp_solve_batch(qlamd_context *ctx, int n, int p, int m, const double *
   const double *dG = G, *dg0 = g0, *dCE = CE, *dce0 = ce0, *dCI = CI, *dci0 = ci0;
   double *dx = x, *dobj = objective;
   int32_t *dst = status;
+  Staged sg;
   if (memory == QLAMD_MEM_HOST) {
-    const size_t sz[6] = {B * n * n * 8, B * n * 8, B * n * p * 8, B * p * 8, B * n * m * 8, B * m * 8};
-    const void *src[6] = {G, g0, CE, ce0, CI, ci0};
-    size_t off[9], total = 0;
-    for (int k = 0; k < 6; k++) { off[k] = total; total += align256(sz[k]); }
-    off[6] = total; total += align256(B * n * 8);
-    off[7] = total; total += align256(B * 8);
-    off[8] = total; total += align256(B * 4);
-    int rc = ensure_ws(ctx, total);
+    const int iG = sg.add(G, B * n * n * 8, true, false), ig = sg.add(g0, B * n * 8, true, false);
+    const int iCE = sg.add(CE, B * n * p * 8, true, false), ice = sg.add(ce0, B * p * 8, true, false);
+    const int iCI = sg.add(CI, B * n * m * 8, true, false), ici = sg.add(ci0, B * m * 8, true, false);
+    const int ox = sg.add(x, B * n * 8, false, true), oo = sg.add(objective, B * 8, false, true), os = sg.add(status, B * 4, false, true);
+    const int rc = sg.upload(ctx, st);
     if (rc != QLAMD_OK) return rc;
-    char *w = (char *)ctx->ws;
-    for (int k = 0; k < 6; k++)
-      if (sz[k] && hipMemcpyAsync(w + off[k], src[k], sz[k], hipMemcpyHostToDevice, st) != hipSuccess)
-        return QLAMD_ERR_HIP;
-    dG = (const double *)(w + off[0]); dg0 = (const double *)(w + off[1]); dCE = (const double *)(w + off[2]);
-    dce0 = (const double *)(w + off[3]); dCI = (const double *)(w + off[4]); dci0 = (const double *)(w + off[5]);
-    dx = (double *)(w + off[6]); dobj = objective ? (double *)(w + off[7]) : nullptr; dst = (int32_t *)(w + off[8]);
+    dG = sg.dev<const double>(iG); dg0 = sg.dev<const double>(ig); dCE = sg.dev<const double>(iCE);
+    dce0 = sg.dev<const double>(ice); dCI = sg.dev<const double>(iCI); dci0 = sg.dev<const double>(ici);
+    dx = sg.dev<double>(ox); dobj = sg.dev<double>(oo); dst = sg.dev<int32_t>(os);
   }
   {
     const unsigned cgrid = (unsigned)((batch + coop::kQpCoopRows - 1) / coop::kQpCoopRows);
@@ -641,14 +611,7 @@ int qlamd_qp_solve_batch(qlamd_context *ctx, int n, int p, int m, const double *
   }
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   { const int rc = finish_placement(ctx, pl, batch, st); if (rc != QLAMD_OK) return rc; }
-  if (memory == QLAMD_MEM_HOST) {
-    if (hipMemcpyAsync(x, dx, B * n * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return QLAMD_ERR_HIP;
-    if (objective && hipMemcpyAsync(objective, dobj, B * 8, hipMemcpyDeviceToHost, st) != hipSuccess)
-      return QLAMD_ERR_HIP;
-    if (hipMemcpyAsync(status, dst, B * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return QLAMD_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return QLAMD_ERR_HIP;
-  }
-  return QLAMD_OK;
+  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
 }
 
 int qlamd_weighted_lsq_qp_batch(qlamd_context *ctx, int n, int k, int p, int m, const double *A, const double *S,

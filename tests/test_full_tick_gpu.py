@@ -143,13 +143,18 @@ def test_full_tick_without_a_command_block_skips_malformed_messages(oracle):
     assert io["status"][5] == 4 and io["message_status"][5] != 0
 
 
-def test_full_tick_large_batches_take_the_same_results_through_separate_launches():
+@pytest.fixture(scope="module")
+def large_tick():
+    """One tick's inputs for 33 001 robots (made once: the Python serialiser is the slow part)."""
+    return make_tick_inputs(33001, 0, truncated=(7, 20000))[1]
+
+
+def test_full_tick_large_batches_take_the_same_results_through_separate_launches(large_tick):
     """Up to 16 384 robots the tick is two launches (parser + state machine, balance + swing branch); above, four.  The
     arithmetic is the same: 33 001 robots in one call against the same robots in two calls of half the size, bit for bit
     (the small form is the one the oracle chain is compared with above)."""
     from quadruped_locomotion_amd import capi
-    B, period = 33001, 0.0025
-    msgs, tin = make_tick_inputs(B, 0, truncated=(7, 20000))
+    B, period, tin = 33001, 0.0025, large_tick
     whole = dict(tin, **fresh_state(B, capi))
     whole["command"] = None
     capi.full_tick(capi.Context(), whole, period)
@@ -165,6 +170,25 @@ def test_full_tick_large_batches_take_the_same_results_through_separate_launches
         capi.full_tick(capi.Context(), io, period)
         for k in PERSIST + ("joint_effort", "status", "message_status", "leg_state_code"):
             assert np.array_equal(io[k], whole[k][lo:hi]), (k, lo)
+
+
+def test_large_ticks_ignore_the_state_layout_option(large_tick):
+    """QLAMD_OPT_STATE_LAYOUT is an option of the balance entries: the tick's own arrays are per-field arrays whatever it
+    says.  33 001 robots (the balance solve as a launch of its own) on a context with QLAMD_STATE_RECORDS against a default
+    context: every persistent array, efforts and statuses bit for bit."""
+    from quadruped_locomotion_amd import capi
+    B, period = 33001, 0.0025
+    runs = []
+    for layout in (capi.STATE_FIELDS, capi.STATE_RECORDS):
+        ctx = capi.Context()
+        ctx.set_option(capi.OPT_STATE_LAYOUT, layout)
+        io = dict(large_tick, **fresh_state(B, capi))
+        io["command"] = None
+        capi.full_tick(ctx, io, period)
+        runs.append(io)
+    assert (runs[0]["status"] == 0).sum() > B // 2
+    for k in PERSIST + ("joint_effort", "status", "message_status", "leg_state_code"):
+        assert np.array_equal(runs[1][k], runs[0][k]), k
 
 
 def test_large_ticks_run_the_placed_loop_on_their_own_state():
@@ -210,23 +234,30 @@ def test_large_ticks_run_the_placed_loop_on_their_own_state():
 
 def test_full_tick_on_the_one_lane_balance_kernels():
     """qlamd_set_robots_per_wave(16 | 64) swaps the tick's balance stage onto the one-lane-per-robot kernels (an
-    independent second implementation of the QP): same statuses and state, efforts to the torque tolerance."""
+    independent second implementation of the QP): same statuses and state, efforts to the torque tolerance.  A context with
+    QLAMD_OPT_STATE_LAYOUT = QLAMD_STATE_RECORDS (an option of the balance entries only) ticks as the default one, bit for bit."""
     from quadruped_locomotion_amd import capi
     B, period = 512, 0.0025
     msgs, tin = make_tick_inputs(B, 1, truncated=(9,))
     ref = dict(tin, **fresh_state(B, capi))
     capi.full_tick(capi.Context(), ref, period)
     for rpw in (16, 64):
-        ctx = capi.Context()
-        ctx.set_robots_per_wave(rpw)
-        io = dict(tin, **fresh_state(B, capi))
-        capi.full_tick(ctx, io, period)
+        runs = []
+        for layout in (capi.STATE_FIELDS, capi.STATE_RECORDS):
+            ctx = capi.Context()
+            ctx.set_robots_per_wave(rpw)
+            ctx.set_option(capi.OPT_STATE_LAYOUT, layout)
+            runs.append(dict(tin, **fresh_state(B, capi)))
+            capi.full_tick(ctx, runs[-1], period)
+        io = runs[0]
         for k in PERSIST + ("status", "message_status", "leg_state_code"):
             if k in ("pid_error_last", "pid_error_integral"):
                 assert np.abs(io[k] - ref[k]).max() < 1e-12, k
             else:
                 assert np.array_equal(io[k], ref[k]), k
         assert np.abs(io["joint_effort"] - ref["joint_effort"]).max() < TAU_TOL
+        for k in PERSIST + ("joint_effort", "status", "message_status", "leg_state_code"):
+            assert np.array_equal(runs[1][k], io[k]), (rpw, k)
 
 
 def test_full_tick_keeps_the_previous_efforts_of_a_failed_solve(oracle):

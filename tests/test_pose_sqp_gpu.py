@@ -243,3 +243,43 @@ def test_linearly_dependent_rows_follow_the_reference(gpu, oracle):
                 if st[i] == 0:
                     assert np.abs(r["x"] - x[i]).max() < 1e-8 * max(1.0, np.abs(r["x"]).max()), (build, dummy, i)
             assert (n_inf == B) == (build == "contradictory")
+
+
+@pytest.mark.parametrize("B", [40, 2000])   # below and above the 256 KB up to which a host call goes through one pinned slab
+def test_host_calls_match_device_calls(gpu, B):
+    """The pose SQP, pose QP and dense QP entries on host buffers give what the same calls on device arrays give, bit for bit."""
+    import ctypes as C
+    capi, ctx, torch = gpu
+    L, stream = capi.lib(), torch.cuda.current_stream().cuda_stream
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")  # noqa: E731
+    zeros = lambda *shape, dt=torch.float64: torch.zeros(*shape, dtype=dt, device="cuda:0")  # noqa: E731
+    pb = synth.make_pose_problems(B)
+    prm = capi.default_pose_params()
+    d = {k: dev(v) for k, v in pb.items()}
+    host = capi.pose_sqp(ctx, pb, prm)
+    out = (zeros(B, 7), zeros(B, dt=torch.int32), zeros(B, dt=torch.int32))
+    capi.pose_sqp(ctx, d, prm, memory=capi.MEM_DEVICE, out=out, stream=stream)
+    torch.cuda.synchronize()
+    for h, o in zip(host, out):
+        assert np.array_equal(h, o.cpu().numpy())
+    pose_h, st_h = capi.pose_qp(ctx, pb, prm)
+    pbd, _ = capi._pose_batch(d, capi.MEM_DEVICE)
+    pose_d, st_d = zeros(B, 7), zeros(B, dt=torch.int32)
+    assert L.qlamd_pose_qp_batch(ctx._h, C.byref(prm), C.byref(pbd), B, pose_d.data_ptr(), st_d.data_ptr(), capi.MEM_DEVICE,
+                                 C.c_void_p(stream)) == capi.OK
+    torch.cuda.synchronize()
+    assert np.array_equal(pose_h, pose_d.cpu().numpy()) and np.array_equal(st_h, st_d.cpu().numpy())
+    rng = np.random.default_rng(B)
+    n, p, m = 8, 2, 10
+    M = rng.normal(size=(B, n, n))
+    G, g0 = M @ M.transpose(0, 2, 1) + 1e-2 * np.eye(n), 10 * rng.normal(size=(B, n))
+    CE, ce0 = rng.normal(size=(B, n, p)), rng.normal(size=(B, p))
+    CI, ci0 = rng.normal(size=(B, n, m)), rng.normal(size=(B, m)) + 1.0
+    host = capi.qp_solve(ctx, G, g0, CE, ce0, CI, ci0)
+    ins, out = [dev(a) for a in (G, g0, CE, ce0, CI, ci0)], (zeros(B, n), zeros(B), zeros(B, dt=torch.int32))
+    assert L.qlamd_qp_solve_batch(ctx._h, n, p, m, *[a.data_ptr() for a in ins], B,
+                                  *[o.data_ptr() for o in out], capi.MEM_DEVICE, C.c_void_p(stream)) == capi.OK
+    torch.cuda.synchronize()
+    for h, o in zip(host, out):
+        assert np.array_equal(h, o.cpu().numpy())
+    assert (host[2] == 0).sum() > B // 2
