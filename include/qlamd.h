@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 #define QLAMD_VERSION_MAJOR 0
-#define QLAMD_VERSION_MINOR 6
+#define QLAMD_VERSION_MINOR 7
 
 /* ---- return codes of the API calls ------------------------------------- */
 #define QLAMD_OK 0
@@ -375,7 +375,33 @@ typedef struct qlamd_placement {
    * (solve_quadprog has no warm start, QuadProg++.cc:216-233) -- still what the robot cost, so still the placement hint. */
   const uint32_t *prev_working_set;
   uint32_t *working_set;
+  /* A WORKING SET PER SUPPORT SET, for the same two entries with QLAMD_MEM_DEVICE: set_memory [B][4] (16-byte aligned, zero-filled
+   * before the first step, in/out) takes the place of prev_working_set -- giving both is QLAMD_ERR_INVALID_ARGUMENT -- for a
+   * caller whose robots change their support legs, a gait: one word per robot remembers the set of the last step only, which
+   * belongs to other legs after a contact switch and is thrown away (above); four words remember the set the robot ended with
+   * THE LAST TIME IT STOOD ON THESE LEGS.  Word format as prev_working_set (rows in bits 0..19, the support legs the set was
+   * reached with in bits 20..23, 0 = no record).  The slot of a support mask (LF = bit 0, RF = 1, RH = 2, LH = 3) is
+   * qlamd_set_memory_slot(mask): {LF, RH} -> 0, {RF, LH} -> 1, all four legs -> 2, any other mask -> 3 -- ONE slot shared by
+   * every other support set (the word's bits 20..23 say which of them it holds): a trot has the first three, a gait with more
+   * support sets (a walk, a pace with overlaps) recalls only the most recent of its odd ones.
+   * A robot starts from set_memory[i][slot(its support legs)] if the legs recorded in that word are its support legs now;
+   * otherwise it has no set to start from and does what such a robot does with prev_working_set: it builds one by rounds.  With
+   * status QLAMD_STATUS_OK it writes its final set, with its support legs, to the same slot; with any other status, and when its
+   * start was rejected and the robot solved again from the empty set (QLAMD_OPT_WARM_FALLBACK 1 / 2: the second attempt's
+   * working set comes back 0, as in working_set), it writes 0 there.  The robot's three other slots are neither read for
+   * arithmetic nor written.  working_set may be given as well and receives the final set as without the table; iterations, the
+   * placement (QLAMD_PLACEMENT_AUTO counts the table as a warm start), QLAMD_STATE_RECORDS and per-leg normals work with it as
+   * with prev_working_set, and so do the checks: a word that is no working set is ignored, an answer that fails the final
+   * check is never returned.  Host-memory calls and qlamd_set_robots_per_wave(16 | 64) refuse it as they refuse any warm start.
+   * Not taken by qlamd_place_next_call (QLAMD_ERR_INVALID_ARGUMENT): the whole-body step keeps two words per robot, and
+   * qlamd_full_tick_batch its one-word working_set.  16 bytes read and 4 written per robot and step.
+   * Last member: an initialiser written for the structure without it leaves it NULL. */
+  uint32_t *set_memory;
 } qlamd_placement;
+/* The slot of qlamd_placement::set_memory that belongs to a support mask (bit l = leg l supports; bits above 3 ignored): the
+ * table the kernels use -- QLAMD_SET_MEMORY_SLOT is its one definition. */
+#define QLAMD_SET_MEMORY_SLOT(mask) (((mask) & 15u) == 5u ? 0u : ((mask) & 15u) == 10u ? 1u : ((mask) & 15u) == 15u ? 2u : 3u)
+unsigned qlamd_set_memory_slot(unsigned support_mask);
 int qlamd_balance_solve_placed_batch(qlamd_context *ctx, const qlamd_state_batch *in, int64_t batch,
                                      const qlamd_placement *placement, double *joint_effort, double *contact_force,
                                      int32_t *status, int memory, void *stream);
@@ -391,6 +417,8 @@ int qlamd_force_distribution_placed_batch(qlamd_context *ctx, const double *join
  * robot_order / iterations index the call's problems; with prev_iterations / next_robot_order the placement for the
  * caller's next call is made by qlamd_placement_from_iterations' launches behind the solve, on its stream.
  * placement = NULL withdraws a pending one.  (qlamd_balance_solve_batch and the other entries ignore it.)
+ * A placement with set_memory is refused (QLAMD_ERR_INVALID_ARGUMENT, nothing pending afterwards): the table is the balance
+ * step's.
  * Warm start: qlamd_wholebody_solve_batch also takes prev_working_set / working_set this way, with TWO words per robot
  * ([B][2] uint32 = 64 bits, low word first: bit 11 leg + kind, kinds 0..4 as for the balance step, 5 + 2k / 6 + 2k the upper /
  * lower torque bound of the leg's joint k; bits 44..47: the support legs the set was reached with); the two dense entries start

@@ -30,7 +30,7 @@ EXPORTS = (
     "qlamd_wholebody_default_params", "qlamd_wholebody_dynamics_batch", "qlamd_wholebody_solve_batch",
     "qlamd_full_tick_batch", "qlamd_set_option", "qlamd_tick_command_bytes", "qlamd_weighted_lsq_qp_batch",
     "qlamd_reserve", "qlamd_balance_solve_placed_batch", "qlamd_force_distribution_placed_batch",
-    "qlamd_placement_from_iterations", "qlamd_place_next_call", "qlamd_get_counter",
+    "qlamd_placement_from_iterations", "qlamd_place_next_call", "qlamd_get_counter", "qlamd_set_memory_slot",
 )
 
 
@@ -50,7 +50,7 @@ class Placement(C.Structure):
     """qlamd_placement"""
     _fields_ = [("robot_order", C.c_void_p), ("iterations", C.c_void_p), ("prev_iterations", C.c_void_p),
                 ("next_robot_order", C.c_void_p), ("policy", C.c_int), ("prev_working_set", C.c_void_p),
-                ("working_set", C.c_void_p)]
+                ("working_set", C.c_void_p), ("set_memory", C.c_void_p)]
 
 
 class RobotModel(C.Structure):
@@ -213,6 +213,9 @@ def lib():
             L.qlamd_placement_from_iterations.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
                                                           C.c_void_p]
             L.qlamd_place_next_call.argtypes = [C.c_void_p, C.POINTER(Placement)]
+        if hasattr(L, "qlamd_set_memory_slot"):  # (absent from builds before 0.7, which tools/set_memory_probe.py --lib runs)
+            L.qlamd_set_memory_slot.argtypes = [C.c_uint]
+            L.qlamd_set_memory_slot.restype = C.c_uint
         L.qlamd_virtual_wrench_batch.argtypes = [C.c_void_p, C.POINTER(StateBatch), C.c_int64, C.c_void_p,
                                                  C.c_int, C.c_void_p]
         L.qlamd_leg_kinematics_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
@@ -261,6 +264,12 @@ def lib():
 
 def strerror(code):
     return lib().qlamd_strerror(int(code)).decode()
+
+
+def set_memory_slot(support_mask):
+    """qlamd_set_memory_slot: the slot of qlamd_placement::set_memory [B][4] that belongs to a support mask (LF = bit 0, RF = 1,
+    RH = 2, LH = 3) -- the library's own table, the one its kernels use."""
+    return int(lib().qlamd_set_memory_slot(C.c_uint(int(support_mask))))
 
 
 def default_params():
@@ -375,10 +384,12 @@ class Context:
             raise QlamdError(rc, "qlamd_balance_solve_batch")
 
     def balance_solve_placed_device(self, dstate, tau, grf, status, order=None, iterations=None, prev_iterations=None,
-                                    next_order=None, policy=0, stream=None, prev_working_set=None, working_set=None):
+                                    next_order=None, policy=0, stream=None, prev_working_set=None, working_set=None,
+                                    set_memory=None):
         """qlamd_balance_solve_placed_batch on torch CUDA tensors: order = int32 [B] permutation (slot -> robot) or None,
         iterations = int32 [B] output or None; prev_iterations / next_order = the counts of the previous call and the
-        placement for the next one (both or neither).  Asynchronous."""
+        placement for the next one (both or neither); set_memory = int32 [B, 4], the working set per support set, updated in
+        place (instead of prev_working_set).  Asynchronous."""
         sb = StateBatch()
         B = dstate["q"].shape[0]
         for key, field, _ in FIELD_OF_KEY:
@@ -392,13 +403,29 @@ class Context:
         for name, t in (("prev_working_set", prev_working_set), ("working_set", working_set)):
             if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != B or not t.is_contiguous()):
                 raise ValueError("%s must be a contiguous int32 tensor of %d elements (the 32 bits of a uint32)" % (name, B))
+        _check_set_memory(set_memory, B)
         pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
-                       _ptr(prev_working_set), _ptr(working_set))
+                       _ptr(prev_working_set), _ptr(working_set), _ptr(set_memory))
         rc = lib().qlamd_balance_solve_placed_batch(self._h, C.byref(sb), B, C.byref(pl), tau.data_ptr(),
                                                     grf.data_ptr() if grf is not None else None, status.data_ptr(),
                                                     MEM_DEVICE, C.c_void_p(stream) if stream else None)
         if rc != OK:
             raise QlamdError(rc, "qlamd_balance_solve_placed_batch")
+
+    def force_distribution_placed_device(self, q, quat, support, wrench, tau, grf, status, normals=None, order=None, iterations=None,
+                                         prev_iterations=None, next_order=None, policy=0, stream=None, prev_working_set=None,
+                                         working_set=None, set_memory=None):
+        """qlamd_force_distribution_placed_batch on torch CUDA tensors (q [B, 12], quat [B, 4], support uint8 [B, 4], wrench
+        [B, 6]); the placement's arguments as balance_solve_placed_device.  Asynchronous."""
+        B = q.shape[0]
+        _check_set_memory(set_memory, B)
+        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
+                       _ptr(prev_working_set), _ptr(working_set), _ptr(set_memory))
+        rc = lib().qlamd_force_distribution_placed_batch(self._h, _ptr(q), _ptr(quat), _ptr(support), _ptr(normals), _ptr(wrench), B,
+                                                         C.byref(pl), _ptr(tau), _ptr(grf), _ptr(status), MEM_DEVICE,
+                                                         C.c_void_p(stream) if stream else None)
+        if rc != OK:
+            raise QlamdError(rc, "qlamd_force_distribution_placed_batch")
 
     def balance_solve_placed_host(self, state, order=None, normals=None, want_forces=True, prev_iterations=None, policy=0):
         """qlamd_balance_solve_placed_batch with host (numpy) buffers -> (tau, grf, status, iterations[, next_order])."""
@@ -512,6 +539,12 @@ def _ptr(a):
     if a is None:
         return None
     return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+def _check_set_memory(t, B):
+    """qlamd_placement::set_memory as a torch tensor: int32 [B, 4], contiguous (alignment is the library's to refuse)."""
+    if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != 4 * B or not t.is_contiguous()):
+        raise ValueError("set_memory must be a contiguous int32 tensor of %d x 4 elements (the 32 bits of a uint32)" % B)
 
 
 def _host_out(a, B, name):

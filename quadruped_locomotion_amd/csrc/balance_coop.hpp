@@ -24,6 +24,7 @@
 #pragma once
 
 #include "force_qp_coop.hpp"
+#include "qlamd.h" // QLAMD_SET_MEMORY_SLOT
 
 namespace qlamd {
 namespace coop {
@@ -42,6 +43,8 @@ struct CoopPtrs {
   uint32_t *working_set;
   uint32_t *warm_retries; // the context's count of rejected warm starts (QLAMD_COUNTER_WARM_RETRIES), or NULL
   int record_doubles;     // 0: one array per field; R: the double fields are records of R doubles (QLAMD_STATE_RECORDS)
+  // kTable only: a working set per support set, [B][4] words (qlamd_placement::set_memory) -- in the place of prev_working_set
+  uint32_t *set_memory;
 };
 
 // Support legs first.  The QP's variables are the contact forces of the legs that support; with the legs of a robot laid
@@ -104,7 +107,10 @@ constexpr int kCoopNrmDoubles = 12 * 64; // 5 row kinds + parked Jacobian row (3
 // placed entries, whose sorted placement groups robots by class); without it (the plain entry: who shares a wavefront is an
 // accident of the batch order there, and the second form cost it 3-4 % on batches of robots on four legs) every wavefront
 // takes the 12-variable form, which gives a robot on two legs the same result bit for bit (its padding rows add exact zeros)
-template <bool kPerLeg, int kBlock = 64, bool kWarm = false, bool kParkInputs = false, bool kThroughput = false, bool kSmallForm = true>
+// kTable (with kWarm): the set a robot starts from is the word of its support set in s.set_memory's four, and its final set
+// goes back there -- the set it ended with the last time it stood on these legs, not the one of the step before
+template <bool kPerLeg, int kBlock = 64, bool kWarm = false, bool kParkInputs = false, bool kThroughput = false, bool kSmallForm = true,
+          bool kTable = false>
 __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs &s, int64_t irobot, bool robot_live_in,
                                            double *lds_tab, double *lds_row, double *lds_nrm,
                                            double *__restrict__ tau_out,
@@ -156,7 +162,12 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
   const uint8_t alive = s.live ? s.live[i_in] : (uint8_t)1;
   unsigned warm_set = 0u;
   bool build_set = false;
-  if constexpr (kWarm) warm_set = (s.prev_working_set && !cold) ? s.prev_working_set[i_in] : 0u;
+  static_assert(!kTable || kWarm, "the table is a warm start");
+  // (the table: the robot's four words in one 16-byte load, issued here with the rest -- which of them counts is known once
+  // the support flags have arrived, so there is no second round trip behind them)
+  uint4 mem = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (kTable) mem = reinterpret_cast<const uint4 *>(s.set_memory)[i_in];
+  else if constexpr (kWarm) warm_set = (s.prev_working_set && !cold) ? s.prev_working_set[i_in] : 0u;
   double wr[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // externally supplied (F_B, T_B), if any: issued with the rest
   if (s.wrench) {
 #pragma unroll
@@ -170,6 +181,10 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
                                         ((sm & 0xFF0000u) ? 4u : 0u) | ((sm & 0xFF000000u) ? 8u : 0u))
                                      : 0u;
   const int nS = __popc(stance);
+  if constexpr (kTable) {
+    const unsigned slot = QLAMD_SET_MEMORY_SLOT(stance);
+    warm_set = slot == 0u ? mem.x : slot == 1u ? mem.y : slot == 2u ? mem.z : mem.w;
+  }
   if constexpr (kWarm) {
     // A working set remembers the support legs it was reached with (bits 20..23; 0: not recorded).  A robot that has changed
     // them since -- a trot entering or leaving double support -- starts cold: on the bench's trot trajectory such a robot
@@ -180,7 +195,8 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
     // ... and BUILDS a set by rounds instead of adding a row a pass (force_qp_coop.hpp, kGreedy), as does a robot on its first
     // step (a word of zeros: no record).  A robot that simply ended its last step with no active row is neither: its empty set
     // carries its support legs, and it goes on as the reference's method does.
-    build_set = s.prev_working_set != nullptr && !cold && from != stance;
+    if constexpr (kTable) build_set = from != stance; // (the shared slot holds another support set's word, or none yet)
+    else build_set = s.prev_working_set != nullptr && !cold && from != stance;
   }
   // support legs first: the leg behind my slot, and what was loaded by leg goes to the lane of its slot
   const unsigned perm = slot_legs(stance);
@@ -454,6 +470,7 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
       status_out[i] = kStatusNotPd;
       if (s.iterations) s.iterations[i] = 0;
       if constexpr (kWarm) { if (s.working_set) s.working_set[i] = 0u; }
+      if constexpr (kTable) s.set_memory[4 * i + QLAMD_SET_MEMORY_SLOT((unsigned)parked.y >> 16)] = 0u;
     }
     if (comp && robot_live && !P.keep_on_failure && (on || !s.support_only)) { tau_out[12 * i + aidx] = 0.0; if (grf_out) grf_out[12 * i + aidx] = 0.0; }
     return false;
@@ -484,7 +501,13 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
       status_out[i] = status;
       if (s.iterations) s.iterations[i] = qp_iters;
       if constexpr (kWarm) { // (with the support legs it was reached with: bits 20..23)
-        if (s.working_set) s.working_set[i] = status == kStatusOk ? ((uint32_t)final_set | (((uint32_t)parked.y >> 16 & 0xFu) << 20)) : 0u;
+        const uint32_t word = status == kStatusOk ? ((uint32_t)final_set | (((uint32_t)parked.y >> 16 & 0xFu) << 20)) : 0u;
+        if (s.working_set) s.working_set[i] = word;
+        // (the table: one word, the slot of these support legs; the robot's three others stay as they are.  A robot that goes
+        // through the second attempt ends with 0 there as in working_set -- known here already: a status that is not OK, or
+        // QLAMD_OPT_WARM_FALLBACK 2 and a non-empty set -- so the second attempt, which knows no table, need not come back to it)
+        if constexpr (kTable)
+          s.set_memory[4 * i + QLAMD_SET_MEMORY_SLOT((unsigned)parked.y >> 16)] = (P.warm_fallback == 2 && final_set != 0ull) ? 0u : word;
       }
     }
   }

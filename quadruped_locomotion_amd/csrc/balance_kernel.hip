@@ -4,6 +4,10 @@
 #include "params_build.hpp"
 #include "context.hpp"
 
+#include <cstddef>
+#include <tuple>
+#include <type_traits>
+
 using namespace qlamd;
 using namespace qlamd::rt;
 
@@ -32,6 +36,7 @@ struct StatePtrs {
   uint32_t place_wait;              // polls they wait for each other before they give up (QLAMD_OPT_PLACEMENT_WAIT)
   uint32_t *warm_retries;           // the context's count of rejected warm starts (kWarm instantiations)
   int record_doubles;               // 0, or the record length of QLAMD_STATE_RECORDS (lane-cooperative kernels, device memory)
+  uint32_t *set_memory;             // [B][4] or NULL: a working set per support set (kTable instantiations), instead of prev_working_set
 };
 
 __device__ __forceinline__ void load_robot(const StatePtrs &s, int64_t i, RobotIn &in) {
@@ -469,9 +474,22 @@ __device__ __forceinline__ void placement_wave(const int32_t *__restrict__ iters
 // body as a function of its own that ENDS THE WAVEFRONT -- nothing of the caller's is live across the call -- and takes what it
 // needs from the kernel's argument segment again (coop::kernel_arguments_again: the caller passes the segment's address -- a
 // function that is not a kernel has none of its own -- and keeps nothing else for it).
+// (BalanceCoopArgs mirrors the parameters of balance_coop_kernel by hand: the checks behind the kernel tie the two together)
 struct BalanceCoopArgs { const DeviceParams *Pp; StatePtrs s; int64_t B; double *tau, *grf; int32_t *status; }; // the kernel's parameters
+// Where a kernel's parameters lie in its argument segment: each at its natural alignment, in the order of the signature
+template <class F> struct KernargLayout;
+template <class... P> struct KernargLayout<void (*)(P...)> {
+  static constexpr size_t count = sizeof...(P);
+  static constexpr size_t offset(size_t k) { // (k == count: the length of the segment's explicit part)
+    const size_t size[] = {sizeof(P)...}, align[] = {alignof(P)...};
+    size_t o = 0;
+    for (size_t j = 0; j < k; j++) o = (o + align[j] - 1) / align[j] * align[j] + size[j];
+    return k < count ? (o + align[k] - 1) / align[k] * align[k] : o;
+  }
+  template <size_t k> using type = std::tuple_element_t<k, std::tuple<P...>>;
+};
 template <bool kPerLeg, int kMinWaves>
-__device__ __attribute__((noinline, noreturn)) void balance_cold_retry(const BalanceCoopArgs *args, double *lds, bool rejected) {
+__device__ __forceinline__ void cold_retry_body(const BalanceCoopArgs *args, double *lds, bool rejected) {
   const BalanceCoopArgs &a = *args;
   double *tab = lds, *rows = lds + 4 * kTabPerLeg, *nrm = rows + 4 * coop::kCoopLdsDoubles;
   const int row = threadIdx.x >> 4;
@@ -487,6 +505,18 @@ __device__ __attribute__((noinline, noreturn)) void balance_cold_retry(const Bal
                             a.s.normals, a.s.wrench, a.s.live, a.s.support_only, a.s.iterations, nullptr, nullptr, nullptr, a.s.record_doubles};
   (void)coop::coop_robot<kPerLeg, 64, false, kMinWaves == 3>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.tau, a.grf, a.status);
   if (rejected && (threadIdx.x & 15) == 0 && a.s.working_set) a.s.working_set[ir] = 0u;
+}
+template <bool kPerLeg, int kMinWaves>
+__device__ __attribute__((noinline, noreturn)) void balance_cold_retry(const BalanceCoopArgs *args, double *lds, bool rejected) {
+  cold_retry_body<kPerLeg, kMinWaves>(args, lds, rejected);
+  __builtin_amdgcn_endpgm();
+}
+// ... of the kernels that start from the table (balance_table_kernel): the same body -- the first attempt has written the table's
+// word already -- as a function of its own, because a function with two callers saves what it would clobber: 40-136 bytes more
+// scratch in every warm-started launch
+template <bool kPerLeg, int kMinWaves>
+__device__ __attribute__((noinline, noreturn)) void balance_table_retry(const BalanceCoopArgs *args, double *lds, bool rejected) {
+  cold_retry_body<kPerLeg, kMinWaves>(args, lds, rejected);
   __builtin_amdgcn_endpgm();
 }
 
@@ -515,71 +545,41 @@ constexpr int kCoopWaves = 1;
 // robot index is one more load in front of the robot's own (a dependent round trip at the head of the launch), which is
 // why the plain entry keeps a kernel without it.  An entry outside [0, B) leaves its row empty.
 // kWarm (with kPlaced): every robot's QP starts from the working set the caller hands in (force_qp_coop.hpp).
+// kTable (with kWarm; balance_table_kernel): ... from the word of its support set in the caller's table of four, s.set_memory
+// (balance_coop.hpp).
+constexpr int kCoopLdsTotal = 4 * kTabPerLeg + 4 * kCoopWaves * coop::kCoopLdsDoubles + kCoopWaves * coop::kCoopNrmDoubles;
+static_assert(kCoopLdsTotal * sizeof(double) >= kShadowLdsBytes || kCoopWaves != 1, "the shadow wavefronts' counters live in the solve's LDS");
 template <bool kPerLeg, int kMinWaves, bool kPlaced = false, bool kWarm = false>
 __global__ __launch_bounds__(64 * kCoopWaves, kMinWaves) void balance_coop_kernel(const DeviceParams *__restrict__ Pp, const StatePtrs s,
                                                                       int64_t B, double *__restrict__ tau,
                                                                       double *__restrict__ grf, int32_t *__restrict__ status) {
-  __shared__ double lds[4 * kTabPerLeg + 4 * kCoopWaves * coop::kCoopLdsDoubles + kCoopWaves * coop::kCoopNrmDoubles];
-  static_assert(sizeof(lds) >= kShadowLdsBytes || kCoopWaves != 1, "the shadow wavefronts' counters live in the solve's LDS");
-  double *tab = lds, *rows = lds + 4 * kTabPerLeg, *nrm = rows + 4 * kCoopWaves * coop::kCoopLdsDoubles;
-  const DeviceParams &P = *Pp;
-  const int row = threadIdx.x >> 4, wave = threadIdx.x >> 6;
-  unsigned block = blockIdx.x;
-  QL_BLOCK_STAMP(0);
-  if constexpr (kPlaced) {
-    // the first workgroups of a launch that also places the next one (they start first and have the whole launch to finish in)
-    if (s.shadow_blocks) {
-      if (block < (unsigned)s.shadow_blocks) {
-        placement_wave(s.prev_iterations, B, s.place_throughput, s.next_order, (lds_u32 *)lds, block, (uint32_t)s.shadow_blocks,
-                       (uint32_t)s.shadow_chunk, s.place_throughput ? reinterpret_cast<const uint32_t *>(s.stance) : nullptr, s.place_hist, s.place_sync,
-                       s.place_wait);
-        return;
-      }
-      block -= (unsigned)s.shadow_blocks;
-      // the wavefronts that solve go first wherever one of them shares a SIMD with a shadow wavefront (which has the whole
-      // launch to finish in): without it the placed loop of 4096 robots is 0.4 us longer with four shadow wavefronts than
-      // with one (profiles/r5/ab_shadow_blocks.txt)
-      __builtin_amdgcn_s_setprio(3);
-    }
-  }
-  int64_t i = (int64_t)block * (4 * kCoopWaves) + row;
-  bool live = i < B;
-  if (!live) i = B - 1;
-  if constexpr (kPlaced) {
-    if constexpr (kMinWaves == 2) { // (QLAMD_PLACEMENT_NONE: the batch order; the 168-register form has no register for it -- a launch of its own there)
-      if (s.shadow_blocks == 0 && s.next_order && live && (threadIdx.x & 15) == 0) s.next_order[i] = (int32_t)i;
-    }
-    if (s.order) {
-      const int64_t o = s.order[i];
-      live = live && o >= 0 && o < B;
-      i = live ? o : B - 1;
-    }
-  }
-  const coop::CoopPtrs cp{s.q, s.pos, s.quat, s.linvel, s.angvel, s.dpos, s.dquat, s.dlinvel, s.dangvel, s.stance,
-                          s.normals, s.wrench, s.live, s.support_only, kPlaced ? s.iterations : nullptr,
-                          kWarm ? s.prev_working_set : nullptr, kWarm ? s.working_set : nullptr, kWarm ? s.warm_retries : nullptr,
-                          s.record_doubles};
-#ifdef QLAMD_STAMPS
-#pragma unroll 1
-  for (int rep = 0; rep < 2; rep++) // second pass runs with a warm instruction cache
-#endif
-  // (inputs parked in LDS across the first form of the QP: the 168-register form solving cold -- no scratch then, 1-2 % on 65 536
-  // to a million robots; the warm-started kernel is 3 % faster with them in registers and 20 bytes of scratch around the loop)
-  {
-    const bool rejected = coop::coop_robot<kPerLeg, 64 * kCoopWaves, kWarm, kMinWaves == 3 && !kWarm && kPlaced, kMinWaves == 3, kPlaced>(
-        P, cp, i, live, tab, rows + row * coop::kCoopLdsDoubles, nrm + wave * coop::kCoopNrmDoubles, tau, grf, status);
-    QL_BLOCK_STAMP(3);
-    if constexpr (kWarm) {
-      // A warm start must never cost an answer (balance_coop.hpp): the rows whose warm start was rejected are solved again, cold,
-      // by this wavefront -- the plain kernel's body behind a scalar branch, everything it needs fetched again from the argument
-      // segment (coop::kernel_arguments_again), the other rows riding along empty; the robot's working set comes back 0.
-      if (__builtin_expect(P.warm_fallback && __builtin_amdgcn_ballot_w64(rejected) != 0ull, 0)) {
-        __syncthreads(); // (one wavefront: the first attempt's LDS reads are done before the table is staged again)
-        balance_cold_retry<kPerLeg, kMinWaves>(coop::kernel_arguments_again<BalanceCoopArgs>(), lds, rejected);
-      }
-    }
-  }
+  __shared__ double lds[kCoopLdsTotal];
+  constexpr bool kTable = false;
+#include "balance_coop_body.hpp"
 }
+// placed, warm-started from the table (qlamd_placement::set_memory): a kernel of its own, so that a launch without the table
+// runs what it ran before the table existed
+template <bool kPerLeg, int kMinWaves>
+__global__ __launch_bounds__(64 * kCoopWaves, kMinWaves) void balance_table_kernel(const DeviceParams *__restrict__ Pp, const StatePtrs s,
+                                                                       int64_t B, double *__restrict__ tau,
+                                                                       double *__restrict__ grf, int32_t *__restrict__ status) {
+  __shared__ double lds[kCoopLdsTotal];
+  constexpr bool kPlaced = true, kWarm = true, kTable = true;
+#include "balance_coop_body.hpp"
+}
+// balance_cold_retry reads the kernel's arguments through BalanceCoopArgs laid over the argument segment: same members, same
+// types, same places as the parameters of the kernels (every instantiation of the two has the one signature)
+using CoopKernelLayout = KernargLayout<decltype(&balance_coop_kernel<false, 2, true, true>)>;
+#define QL_ARG_MATCHES(k, member)                                                                                   \
+  static_assert(std::is_same<CoopKernelLayout::type<k>, decltype(BalanceCoopArgs::member)>::value &&                  \
+                    CoopKernelLayout::offset(k) == offsetof(BalanceCoopArgs, member),                               \
+                "BalanceCoopArgs::" #member " is not parameter " #k " of balance_coop_kernel")
+static_assert(CoopKernelLayout::count == 6, "balance_coop_kernel has grown a parameter: BalanceCoopArgs has to grow with it");
+QL_ARG_MATCHES(0, Pp); QL_ARG_MATCHES(1, s); QL_ARG_MATCHES(2, B); QL_ARG_MATCHES(3, tau); QL_ARG_MATCHES(4, grf); QL_ARG_MATCHES(5, status);
+#undef QL_ARG_MATCHES
+static_assert(CoopKernelLayout::offset(6) == sizeof(BalanceCoopArgs), "BalanceCoopArgs is not as long as the kernel's parameters");
+static_assert(std::is_same<decltype(&balance_coop_kernel<false, 2, true, true>), decltype(&balance_table_kernel<true, 3>)>::value,
+              "balance_table_kernel takes the parameters of balance_coop_kernel");
 
 __global__ __launch_bounds__(64) void virtual_wrench_kernel(const DeviceParams *__restrict__ Pp, const StatePtrs s,
                                                             int64_t B, double *__restrict__ wrench) {
@@ -676,6 +676,7 @@ extern "C" {
 void qlamd_balance_default_params(qlamd_balance_params *p) { if (p) default_balance_params(p); }
 void qlamd_default_robot_model(qlamd_robot_model *m) { if (m) default_robot_model(m); }
 int qlamd_version(void) { return QLAMD_VERSION_MAJOR * 1000 + QLAMD_VERSION_MINOR; }
+unsigned qlamd_set_memory_slot(unsigned support_mask) { return QLAMD_SET_MEMORY_SLOT(support_mask); }
 
 
 const char *qlamd_strerror(int code) {
@@ -887,7 +888,8 @@ int qlamd::rt::placement_launch(qlamd_context *ctx, const int32_t *d_iterations,
 int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, int layout, const double *wrench, const uint8_t *live,
                               int support_only, const qlamd_placement &pl, int64_t batch, double *d_tau, double *d_grf,
                               int32_t *d_status, hipStream_t st) {
-  const bool warm = pl.prev_working_set || pl.working_set;
+  const bool table = pl.set_memory != nullptr; // (instead of prev_working_set: the entries have checked that)
+  const bool warm = pl.prev_working_set || pl.working_set || table;
   // (prev_working_set == working_set is fine: a robot's set is read and written by its own 16 lanes only -- updated in place)
   const bool placed = pl.robot_order || pl.iterations || pl.next_robot_order || warm;
   const int policy = pl.next_robot_order ? effective_policy(pl.policy, batch, warm) : QLAMD_PLACEMENT_NONE;
@@ -897,6 +899,7 @@ int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, i
   s.record_doubles = layout == QLAMD_STATE_RECORDS ? QLAMD_STATE_RECORD_DOUBLES : 0;
   s.prev_working_set = pl.prev_working_set;
   s.working_set = pl.working_set;
+  s.set_memory = pl.set_memory;
   s.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
   // the next launch's placement: by extra wavefronts in front of this launch
   const int chunk = batch >= QLAMD_THROUGHPUT_BATCH ? kShadowChunkLarge : (warm ? kShadowChunkWarm : kShadowChunkCold);
@@ -921,7 +924,10 @@ int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, i
       const unsigned grid = (unsigned)((batch + 4 * kCoopWaves - 1) / (4 * kCoopWaves)) + (unsigned)s.shadow_blocks;
 #define QL_LAUNCH_COOP(PERLEG, WAVES)                                                                                        \
   do {                                                                                                                       \
-    if (warm)                                                                                                                \
+    if (table)                                                                                                               \
+      hipLaunchKernelGGL((balance_table_kernel<PERLEG, WAVES>), dim3(grid), dim3(64 * kCoopWaves), 0, st, ctx->d_params, s,  \
+                         batch, d_tau, d_grf, d_status);                                                                     \
+    else if (warm)                                                                                                           \
       hipLaunchKernelGGL((balance_coop_kernel<PERLEG, WAVES, true, true>), dim3(grid), dim3(64 * kCoopWaves), 0, st,         \
                          ctx->d_params, s, batch, d_tau, d_grf, d_status);                                                   \
     else if (placed)                                                                                                         \
@@ -959,7 +965,9 @@ int balance_entry(qlamd_context *ctx, const qlamd_state_batch *in_user, const do
   memset(&p, 0, sizeof(p));
   if (pl) p = *pl;
   if (!placement_ok(p)) return QLAMD_ERR_INVALID_ARGUMENT;
-  const bool warm = p.prev_working_set || p.working_set;
+  // the table takes the place of prev_working_set, and its robots' four words are one 16-byte load
+  if (p.set_memory && (p.prev_working_set || (reinterpret_cast<uintptr_t>(p.set_memory) & 15u))) return QLAMD_ERR_INVALID_ARGUMENT;
+  const bool warm = p.prev_working_set || p.working_set || p.set_memory;
   if (warm && memory != QLAMD_MEM_DEVICE) return QLAMD_ERR_INVALID_ARGUMENT; // (a host-buffer call is bound by its copies)
   const bool placed = p.robot_order || p.iterations || p.next_robot_order || warm;
   // the one-lane kernels of qlamd_set_robots_per_wave know no placement (a lane is a robot there: nothing is shared)
@@ -1079,7 +1087,8 @@ int qlamd_place_next_call(qlamd_context *ctx, const qlamd_placement *placement) 
   QL_ENTER_NO_STREAM(ctx);
   ctx->has_next_placement = false;
   if (!placement) return QLAMD_OK;
-  if (!placement_ok(*placement)) return QLAMD_ERR_INVALID_ARGUMENT;
+  // (the table of the balance step: the whole-body step keeps two words per robot, the dense entries start cold)
+  if (!placement_ok(*placement) || placement->set_memory) return QLAMD_ERR_INVALID_ARGUMENT;
   ctx->next_placement = *placement;
   ctx->has_next_placement = true;
   return QLAMD_OK;

@@ -1,0 +1,424 @@
+"""qlamd_placement::set_memory -- a working set per support set -- on the GPU: the caller's loop of include/qlamd.h with the table
+[B][4] in the place of the one-word array, stepped through trajectories long enough (two gait cycles of a trot) for every robot
+to come back to legs it has stood on before.  The existing one-word loop, which this change leaves alone, is the yardstick for
+what the table buys; the oracle is the yardstick for every answer."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from quadruped_locomotion_amd import synth
+
+pytestmark = pytest.mark.gpu
+TAU_TOL = 1e-6
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    from quadruped_locomotion_amd import capi
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    capi.lib()
+    ctx = capi.Context(device=0)
+    yield capi, ctx, torch
+    ctx.close()
+
+
+def support_mask(stance):
+    return ((np.asarray(stance) != 0).astype(np.int64) * np.array([1, 2, 4, 8])).sum(1)
+
+
+def slots_of(capi, stance):
+    table = np.array([capi.set_memory_slot(m) for m in range(16)])
+    return table[support_mask(stance)]
+
+
+def trajectory_ticks(B, gait, T, errors=None):
+    """synth.trajectory, one tick at a time (a large batch over hundreds of ticks does not have to sit in memory at once)"""
+    s = synth.make_states(B, gait, errors=errors)
+    phase = synth.trot_phase(B) if gait == "trot" else None
+    yield s
+    for t in range(1, T):
+        s = synth.next_tick_states(s, synth.CONTROL_PERIOD)
+        if gait == "trot":
+            s["stance"] = synth.trot_stance(phase + t * synth.CONTROL_PERIOD / (synth.T_SWING + synth.T_STANCE))
+        yield s
+
+
+def run_loop(gpu, states, table, check=None, to_device=None, normals=None):
+    """The caller's loop over the ticks of `states` (an iterable of state dicts): placement from the counts of tick k - 2 and a
+    warm start from the table (set_memory, with working_set as a plain output) or from the one-word array updated in place.
+    check(k, state, tau, status) per tick.  Returns per tick: iterations, working_set, the support masks, and (table) the word
+    each robot started from -- read from the table before the call -- plus the final table / array."""
+    capi, ctx, torch = gpu
+    stream = torch.cuda.current_stream().cuda_stream
+    out, B, order, iters, ws, mem = [], None, None, None, None, None
+    for k, s in enumerate(states):
+        if B is None:
+            B = s["q"].shape[0]
+            order = [torch.arange(B, dtype=torch.int32, device="cuda:0") for _ in range(2)]
+            iters = [torch.zeros(B, dtype=torch.int32, device="cuda:0") for _ in range(2)]
+            ws = torch.zeros(B, dtype=torch.int32, device="cuda:0")
+            mem = torch.zeros(B, 4, dtype=torch.int32, device="cuda:0")
+        if normals is not None:
+            s = dict(s, normals=normals)
+        d = (to_device or capi.to_device)(s)
+        tau = torch.full((B, 12), np.nan, dtype=torch.float64, device="cuda:0")
+        status = torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+        started = None
+        if table:
+            started = mem.cpu().numpy().view(np.uint32)[np.arange(B), slots_of(capi, s["stance"])]
+        ctx.balance_solve_placed_device(d, tau, None, status, order=order[k & 1], iterations=iters[k & 1],
+                                        prev_iterations=iters[(k - 1) & 1], next_order=order[(k + 1) & 1],
+                                        policy=capi.PLACEMENT_AUTO, prev_working_set=None if table else ws, working_set=ws,
+                                        set_memory=mem if table else None, stream=stream)
+        torch.cuda.synchronize()
+        nxt = order[(k + 1) & 1].cpu().numpy()
+        assert np.array_equal(np.sort(nxt), np.arange(B)), k          # a permutation, whatever the hints were
+        tau_h, status_h = tau.cpu().numpy(), status.cpu().numpy()
+        out.append(dict(iters=iters[k & 1].cpu().numpy().copy(), ws=ws.cpu().numpy().view(np.uint32).copy(), tau=tau_h, status=status_h,
+                        mask=support_mask(s["stance"]), started=started))
+        if check is not None:
+            check(k, s, tau_h, status_h)
+    return out, (mem.cpu().numpy().view(np.uint32) if table else ws.cpu().numpy().view(np.uint32))
+
+
+def oracle_check(capi, oracle, every=1, normals=None):
+    worst = [0.0]
+
+    def check(k, s, tau, status):
+        assert (status != capi.STATUS_WARM_REJECTED).all(), k
+        if k % every:
+            return
+        t0, _, s0 = oracle.balance_batch(s, normals_world=normals, nthreads=16)
+        assert np.array_equal(status, s0), (k, int((status != s0).sum()), np.unique(status))
+        ok = s0 == 0
+        err = np.abs(tau[ok] - t0[ok]).max()
+        worst[0] = max(worst[0], err)
+        assert err < TAU_TOL, (k, err)
+    return check, worst
+
+
+def test_a_static_batch_is_the_one_word_loop_bit_for_bit(gpu):
+    """Robots that never change their support legs: the table is the one-word array in slot 2, every tick, every output."""
+    capi, ctx, torch = gpu
+    B, T = 4096, 32
+    states = synth.trajectory(B, "static", T, errors="survey")
+    word, ws_final = run_loop(gpu, states, table=False)
+    tab, mem_final = run_loop(gpu, states, table=True)
+    for k in range(T):
+        for key in ("tau", "status", "iters", "ws"):
+            assert np.array_equal(word[k][key], tab[k][key], equal_nan=True), (k, key)
+    assert (word[-1]["status"] == 0).all()
+    assert np.array_equal(mem_final[:, 2], ws_final) and (mem_final[:, 2] != 0).any()
+    assert (mem_final[:, [0, 1, 3]] == 0).all()
+
+
+def test_a_trot_over_two_gait_cycles_recalls_its_sets_and_that_pays_in_work(gpu, oracle):
+    """synth.trajectory(1024, "trot", 760), every tick against the oracle.  Then, from tick 400 on, over the robot-ticks whose
+    support set differs from the previous tick's: (a) the word the robot started from carries exactly its support legs of now,
+    for every one of them; (b) their mean `iterations` is strictly below the mean over the SAME robot-ticks in the one-word
+    loop run here on the same trajectory.  Measured on an MI355X: see profiles/r7/set_memory.txt."""
+    capi, ctx, torch = gpu
+    B, T = 1024, 760
+    states = synth.trajectory(B, "trot", T)
+    check, worst = oracle_check(capi, oracle)
+    tab, _ = run_loop(gpu, states, table=True, check=check)
+    word, _ = run_loop(gpu, states, table=False)
+    sw_t, sw_w, same_differs, same_n, recorded_ok, n_sw = [], [], 0, 0, 0, 0
+    for k in range(400, T):
+        switched = tab[k]["mask"] != tab[k - 1]["mask"]
+        n_sw += int(switched.sum())
+        recorded_ok += int((((tab[k]["started"] >> 20) & 0xF)[switched] == tab[k]["mask"][switched]).sum())
+        sw_t.append(tab[k]["iters"][switched])
+        sw_w.append(word[k]["iters"][switched])
+        same_differs += int((tab[k]["iters"][~switched] != word[k]["iters"][~switched]).sum())
+        same_n += int((~switched).sum())
+    mean_t, mean_w = float(np.concatenate(sw_t).mean()), float(np.concatenate(sw_w).mean())
+    all_t = float(np.mean([r["iters"].mean() for r in tab[400:]]))
+    all_w = float(np.mean([r["iters"].mean() for r in word[400:]]))
+    print("trot B=%d T=%d, worst |dtau| %.2e; from tick 400: %d switching robot-ticks, mean iterations table %.3f / one word %.3f; "
+          "all robots table %.3f / one word %.3f; robot-ticks without a switch whose counts differ: %.5f"
+          % (B, T, worst[0], n_sw, mean_t, mean_w, all_t, all_w, same_differs / max(same_n, 1)))
+    assert n_sw > 2000
+    assert recorded_ok == n_sw, (recorded_ok, n_sw)          # (a) every one of them found a set of these legs
+    assert mean_t < mean_w, (mean_t, mean_w)                # (b) and it was less work than building one
+
+
+@pytest.mark.parametrize("B,T", [(8192, 400), (24576, 200)])
+def test_the_table_in_the_other_kernel_forms(gpu, oracle, B, T):
+    """8192 robots (the throughput placement with its support classes) and 24 576 (the 168-register form of the kernel) through
+    more than one support switch per robot class, oracle-checked every 8th tick."""
+    capi, ctx, torch = gpu
+    check, worst = oracle_check(capi, oracle, every=8)
+    seen = dict(recalled=0, switched=0)
+    out, mem = run_loop(gpu, trajectory_ticks(B, "trot", T), table=True, check=check)
+    for k in range(1, T):
+        switched = out[k]["mask"] != out[k - 1]["mask"]
+        seen["switched"] += int(switched.sum())
+        seen["recalled"] += int(((((out[k]["started"] >> 20) & 0xF) == out[k]["mask"]) & switched).sum())
+    print("trot B=%d T=%d: worst |dtau| %.2e, %d switching robot-ticks, %d of them started from a remembered set"
+          % (B, T, worst[0], seen["switched"], seen["recalled"]))
+    assert seen["switched"] > B // 2
+    if T > 360 // 2 + 45:                                   # (the first robots are back on legs they have stood on after 0.45 s)
+        assert seen["recalled"] > 0
+    # every word in the table is a record of the slot's own support set (the trot uses slots 0, 1, 2 only)
+    legs = (mem >> 20) & 0xF
+    assert np.isin(legs[:, 0], (0, 0b0101)).all() and np.isin(legs[:, 1], (0, 0b1010)).all() and np.isin(legs[:, 2], (0, 0b1111)).all()
+    assert (mem[:, 3] == 0).all()
+
+
+def test_a_solve_that_fails_leaves_zero_in_its_slot_and_the_others_alone(gpu):
+    capi, ctx, torch = gpu
+    B = 4096
+    s = synth.make_states(B, "trot")
+    slot = slots_of(capi, s["stance"])
+    rng = np.random.default_rng(3)
+    broken = rng.choice(B, size=37, replace=False)
+    s["q"] = s["q"].copy()
+    s["q"][broken] = np.nan                                   # NaN foot positions: QLAMD_STATUS_NOT_PD
+    marks = rng.integers(1, 1 << 32, size=(B, 4), dtype=np.uint64).astype(np.uint32)
+    marks[np.arange(B), slot] = 0                             # (the slot in use starts without a record)
+    mem = torch.from_numpy(marks.view(np.int32).copy()).to("cuda:0")
+    tau = torch.full((B, 12), np.nan, dtype=torch.float64, device="cuda:0")
+    status = torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+    ctx.balance_solve_placed_device(capi.to_device(s), tau, None, status, set_memory=mem)
+    torch.cuda.synchronize()
+    st, got = status.cpu().numpy(), mem.cpu().numpy().view(np.uint32)
+    assert (st[broken] == capi.STATUS_NOT_PD).all() and (np.delete(st, broken) == 0).all()
+    assert (got[broken, slot[broken]] == 0).all()
+    ok = np.setdiff1d(np.arange(B), broken)
+    assert (((got[ok, slot[ok]] >> 20) & 0xF) == support_mask(s["stance"])[ok]).all()
+    others = np.ones((B, 4), dtype=bool)
+    others[np.arange(B), slot] = False
+    assert np.array_equal(got[others], marks[others])         # the three other slots of every robot: untouched
+    # a failed robot that had a record loses it
+    ctx.balance_solve_placed_device(capi.to_device(synth.make_states(B, "trot")), tau, None, status, set_memory=mem)
+    ctx.balance_solve_placed_device(capi.to_device(s), tau, None, status, set_memory=mem)
+    torch.cuda.synchronize()
+    got = mem.cpu().numpy().view(np.uint32)
+    assert (got[broken, slot[broken]] == 0).all() and (got[ok, slot[ok]] != 0).all()
+
+
+def test_junk_in_the_table_never_costs_an_answer(gpu, oracle):
+    """The junk sets of test_trajectory_gpu.py's rejected-warm-start test, in all four slots, with and without the right support
+    legs recorded: with the fallback on, statuses and efforts are the cold run's; a rejection shows with QLAMD_OPT_WARM_FALLBACK 0
+    only, as QLAMD_STATUS_WARM_REJECTED with zero efforts and 0 in the slot."""
+    capi, ctx, torch = gpu
+    B = 16384 + 3
+    rng = np.random.default_rng(11)
+    stream = torch.cuda.current_stream().cuda_stream
+    seen = 0
+    for gait, errors in (("static", "survey"), ("trot", None)):
+        s = synth.make_states(B, gait, errors=errors)
+        d = capi.to_device(s)
+        slot, legs = slots_of(capi, s["stance"]), support_mask(s["stance"]).astype(np.uint32)
+        t0, _, s0 = oracle.balance_batch(s, nthreads=16)
+        assert (s0 == 0).all()
+        tc = torch.full((B, 12), np.nan, dtype=torch.float64, device="cuda:0")
+        sc = torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+        ctx.balance_solve_device(d, tc, None, sc, stream=stream)
+        torch.cuda.synchronize()
+        tc, sc = tc.cpu().numpy(), sc.cpu().numpy()
+        for junk in (rng.integers(0, 1 << 20, size=(B, 4), dtype=np.uint32), np.full((B, 4), (1 << 20) - 1, dtype=np.uint32),
+                     rng.integers(0, 1 << 32, size=(B, 4), dtype=np.uint64).astype(np.uint32),
+                     np.full((B, 4), 0b01011_10101_01110_10011, dtype=np.uint32)):
+            for right_legs in (False, True):
+                words = junk.copy()
+                if right_legs:   # rows that have nothing to do with the state, under the robot's own support legs: they are installed
+                    words[np.arange(B), slot] = (words[np.arange(B), slot] & 0xFFFFF) | (legs << 20)
+                out = {}
+                for fallback in (0, 1):
+                    ctx.set_option(capi.OPT_WARM_FALLBACK, fallback)
+                    try:
+                        before = ctx.counter(capi.COUNTER_WARM_RETRIES)
+                        tau = torch.full((B, 12), np.nan, dtype=torch.float64, device="cuda:0")
+                        status = torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+                        mem = torch.from_numpy(words.view(np.int32).copy()).to("cuda:0")
+                        ctx.balance_solve_placed_device(d, tau, None, status, set_memory=mem, stream=stream)
+                        torch.cuda.synchronize()
+                        out[fallback] = (tau.cpu().numpy(), status.cpu().numpy(), mem.cpu().numpy().view(np.uint32),
+                                         ctx.counter(capi.COUNTER_WARM_RETRIES) - before)
+                    finally:
+                        ctx.set_option(capi.OPT_WARM_FALLBACK, 1)
+                t_off, s_off, m_off, n_off = out[0]
+                t_on, s_on, m_on, n_on = out[1]
+                rej = s_off == capi.STATUS_WARM_REJECTED
+                assert n_off == rej.sum() == n_on
+                assert (s_off[~rej] == 0).all()
+                assert (t_off[rej] == 0.0).all() and (m_off[rej, slot[rej]] == 0).all()
+                assert np.array_equal(s_on, sc)                                  # never visible with the fallback on
+                assert np.abs(t_on - tc).max() < TAU_TOL and np.abs(t_on - t0).max() < TAU_TOL
+                assert (m_on[rej, slot[rej]] == 0).all()                         # a rejected set is never returned
+                for m in (m_off, m_on):
+                    others = np.ones((B, 4), dtype=bool)
+                    others[np.arange(B), slot] = False
+                    assert np.array_equal(m[others], words[others])
+                    good = ~rej
+                    assert (((m[good, slot[good]] >> 20) & 0xF) == legs[good]).all()
+                seen += int(rej.sum())
+    print("%d rejected starts from the table, none of them visible with the fallback on" % seen)
+
+
+def _tilted_normals(B, seed=5):
+    rng = np.random.default_rng(seed)
+    n = np.tile(np.array([0.0, 0.0, 1.0]), (B, 4, 1)) + rng.normal(scale=0.08, size=(B, 4, 3))
+    return np.ascontiguousarray(n / np.linalg.norm(n, axis=2, keepdims=True))
+
+
+@pytest.mark.parametrize("gait,errors,B,normals", [("static", "survey", 4096, False), ("trot", None, 4099, False), ("trot", None, 22531, False),
+                                                   ("static", "survey", 2051, True)])
+def test_the_second_attempt_at_will_with_the_table(gpu, oracle, gait, errors, B, normals):
+    """QLAMD_OPT_WARM_FALLBACK 2 in every form of the kernel (two wavefronts a SIMD, the 168-register form from 22 528 robots,
+    per-leg normals): every robot that ends its start from the table with a non-empty set goes through the second attempt; the
+    answers are the plain entry's, and the slot holds what the second attempt leaves -- what working_set receives, 0."""
+    capi, ctx, torch = gpu
+    s = synth.make_states(B, gait, errors=errors)
+    if normals:
+        s["normals"] = _tilted_normals(B)
+    d = capi.to_device(s)
+    slot = slots_of(capi, s["stance"])
+    stream = torch.cuda.current_stream().cuda_stream
+    nan = lambda *shape: torch.full(shape, np.nan, dtype=torch.float64, device="cuda:0")  # noqa: E731
+    tp, sp = nan(B, 12), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+    ctx.balance_solve_device(d, tp, None, sp, stream=stream)
+    mem = torch.zeros(B, 4, dtype=torch.int32, device="cuda:0")
+    t1, s1 = nan(B, 12), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+    ctx.balance_solve_placed_device(d, t1, None, s1, set_memory=mem, stream=stream)     # fills the table: every robot builds a set
+    torch.cuda.synchronize()
+    assert (s1 == 0).all() and (t1 - tp).abs().max().item() < 1e-7
+    m1 = mem.cpu().numpy().view(np.uint32).copy()
+    nonempty = (m1[np.arange(B), slot] & 0xFFFFF) != 0
+    assert nonempty.sum() > B // 10
+    order = torch.from_numpy(np.random.default_rng(1).permutation(B).astype(np.int32)).to("cuda:0")
+    ctx.set_option(capi.OPT_WARM_FALLBACK, 2)
+    try:
+        before = ctx.counter(capi.COUNTER_WARM_RETRIES)
+        t2, s2 = nan(B, 12), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+        it2 = torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+        ws2 = torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+        ctx.balance_solve_placed_device(d, t2, None, s2, order=order, iterations=it2, working_set=ws2, set_memory=mem, stream=stream)
+        torch.cuda.synchronize()
+        retried = ctx.counter(capi.COUNTER_WARM_RETRIES) - before
+    finally:
+        ctx.set_option(capi.OPT_WARM_FALLBACK, 1)
+    m2 = mem.cpu().numpy().view(np.uint32)
+    mine = m2[np.arange(B), slot]
+    again = (mine == 0) & nonempty
+    assert retried == again.sum() and again.sum() > 0.95 * nonempty.sum()
+    assert np.array_equal(mine, ws2.cpu().numpy().view(np.uint32))        # the slot holds what working_set receives
+    assert (s2 == 0).all() and (it2 >= 0).all()
+    a = torch.from_numpy(again).to("cuda:0")
+    assert (t2[a] - tp[a]).abs().max().item() < 1e-9 and (t2 - tp).abs().max().item() < 1e-7
+    others = np.ones((B, 4), dtype=bool)
+    others[np.arange(B), slot] = False
+    assert (m2[others] == 0).all()
+    if not normals:
+        to, _, so = oracle.balance_batch(s, nthreads=16)
+        assert np.abs(t2.cpu().numpy() - to).max() < TAU_TOL and np.array_equal(s2.cpu().numpy(), so)
+    # the next step of those robots has no record and builds a set again: as good as any
+    t3, s3 = nan(B, 12), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+    ctx.balance_solve_placed_device(d, t3, None, s3, set_memory=mem, stream=stream)
+    torch.cuda.synchronize()
+    assert (s3 == 0).all() and (t3 - tp).abs().max().item() < 1e-7
+    assert np.array_equal(mem.cpu().numpy().view(np.uint32), m1)
+
+
+def test_refusals(gpu):
+    capi, ctx, torch = gpu
+    B = 1024
+    s = synth.make_states(B, "trot")
+    d = capi.to_device(s)
+    nan = lambda: torch.full((B, 12), np.nan, dtype=torch.float64, device="cuda:0")  # noqa: E731
+    mark = np.random.default_rng(2).integers(1, 1 << 20, size=(B, 4), dtype=np.uint32)
+
+    def refused(**kw):
+        tau, status = nan(), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+        with pytest.raises(capi.QlamdError) as e:
+            ctx.balance_solve_placed_device(d, tau, None, status, **kw)
+        torch.cuda.synchronize()
+        assert e.value.code == capi.ERR_INVALID_ARGUMENT
+        assert torch.isnan(tau).all() and (status == -1).all()               # nothing written
+
+    mem = torch.from_numpy(mark.view(np.int32).copy()).to("cuda:0")
+    ws = torch.zeros(B, dtype=torch.int32, device="cuda:0")
+    refused(prev_working_set=ws, set_memory=mem)                             # the table takes prev_working_set's place
+    refused(prev_working_set=ws, working_set=ws, set_memory=mem)
+    big = torch.from_numpy(np.concatenate([[0], mark.reshape(-1)]).astype(np.uint32).view(np.int32)).to("cuda:0")
+    assert big[1:].data_ptr() % 16 == 4 and big[1:].is_contiguous()
+    refused(set_memory=big[1:])                                              # 16-byte aligned, or not at all
+    ctx.set_robots_per_wave(16)                                              # the one-lane kernels know no warm start
+    try:
+        refused(set_memory=mem)
+    finally:
+        ctx.set_robots_per_wave(0)
+    assert np.array_equal(mem.cpu().numpy().view(np.uint32), mark) and np.array_equal(big.cpu().numpy().view(np.uint32)[1:], mark.reshape(-1))
+
+    # host memory: as any warm start
+    sb, keep = capi.StateBatch(), []
+    for key, field, k in capi.FIELD_OF_KEY:
+        a = np.ascontiguousarray(np.asarray(s[key], dtype=np.float64).reshape(B, k))
+        keep.append(a)
+        setattr(sb, field, a.ctypes.data)
+    st = np.ascontiguousarray(s["stance"], dtype=np.uint8)
+    sb.support_leg = st.ctypes.data
+    host_mem = np.zeros((B + 4, 4), dtype=np.uint32)
+    host_mem = host_mem.reshape(-1)[(-host_mem.ctypes.data // 4) % 4:][:4 * B]   # (16-byte aligned: refused for being host memory)
+    assert host_mem.ctypes.data % 16 == 0
+    tau_h, status_h = np.full((B, 12), np.nan), np.full(B, -1, dtype=np.int32)
+    pl = capi.Placement(set_memory=host_mem.ctypes.data)
+    rc = capi.lib().qlamd_balance_solve_placed_batch(ctx._h, C.byref(sb), B, C.byref(pl), tau_h.ctypes.data, None, status_h.ctypes.data,
+                                                     capi.MEM_HOST, None)
+    assert rc == capi.ERR_INVALID_ARGUMENT and np.isnan(tau_h).all() and (status_h == -1).all() and (host_mem == 0).all()
+
+    # the entries that take their placement from the context (the whole-body step, the dense QPs) and with them the tick: the
+    # table is the balance step's, and the refused placement is not left pending
+    iters = torch.zeros(B, dtype=torch.int32, device="cuda:0")
+    pl = capi.Placement(iterations=iters.data_ptr(), set_memory=mem.data_ptr())
+    assert capi.lib().qlamd_place_next_call(ctx._h, C.byref(pl)) == capi.ERR_INVALID_ARGUMENT
+    ws2 = synth.make_wholebody_states(64, "trot")
+    out = capi.wholebody_solve(ctx, ws2)                                    # host memory: a pending placement would be refused here
+    assert out is not None
+    assert np.array_equal(mem.cpu().numpy().view(np.uint32), mark) and (iters == 0).all()
+
+    # and the force-distribution entry takes the table like the balance entry
+    wrench = torch.zeros(B, 6, dtype=torch.float64, device="cuda:0")
+    ctx.virtual_wrench_device(d, wrench)
+    mem0 = torch.zeros(B, 4, dtype=torch.int32, device="cuda:0")
+    tau, grf, status = nan(), nan(), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+    ctx.force_distribution_placed_device(d["q"], d["base_quat"], d["stance"], wrench, tau, grf, status, set_memory=mem0)
+    tb, sb2 = nan(), torch.full((B,), -1, dtype=torch.int32, device="cuda:0")
+    ctx.balance_solve_device(d, tb, None, sb2)
+    torch.cuda.synchronize()
+    assert (status == 0).all() and (tau - tb).abs().max().item() < 1e-7
+    got = mem0.cpu().numpy().view(np.uint32)
+    slot = slots_of(capi, s["stance"])
+    assert (((got[np.arange(B), slot] >> 20) & 0xF) == support_mask(s["stance"])).all()
+    with pytest.raises(capi.QlamdError) as e:
+        ctx.force_distribution_placed_device(d["q"], d["base_quat"], d["stance"], wrench, tau, grf, status, prev_working_set=ws, set_memory=mem0)
+    assert e.value.code == capi.ERR_INVALID_ARGUMENT
+
+
+def test_records_and_per_leg_normals_with_the_table(gpu, oracle):
+    """16 ticks of a trot each: QLAMD_STATE_RECORDS bit-identical to the per-field arrays (efforts, statuses, counts, sets, the
+    table), per-leg normals equal to the oracle."""
+    capi, ctx, torch = gpu
+    B, T = 4096, 16
+    states = synth.trajectory(B, "trot", T)
+    fields, mem_f = run_loop(gpu, states, table=True)
+    ctx.set_option(capi.OPT_STATE_LAYOUT, capi.STATE_RECORDS)
+    try:
+        records, mem_r = run_loop(gpu, states, table=True, to_device=capi.to_device_records)
+    finally:
+        ctx.set_option(capi.OPT_STATE_LAYOUT, capi.STATE_FIELDS)
+    for k in range(T):
+        for key in ("tau", "status", "iters", "ws", "started"):
+            assert np.array_equal(fields[k][key], records[k][key]), (k, key)
+    assert np.array_equal(mem_f, mem_r) and (fields[-1]["status"] == 0).all()
+
+    Bn = 2051
+    nw = _tilted_normals(Bn)
+    check, worst = oracle_check(capi, oracle, normals=nw.reshape(Bn, 12))
+    out, mem = run_loop(gpu, synth.trajectory(Bn, "trot", T), table=True, check=check, normals=nw.reshape(Bn, 12))
+    assert (mem[np.arange(Bn), slots_of(capi, synth.trajectory(Bn, "trot", T)[-1]["stance"])] != 0).all()
+    print("per-leg normals with the table: worst |dtau| %.2e" % worst[0])
