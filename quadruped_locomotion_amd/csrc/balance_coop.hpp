@@ -24,6 +24,7 @@
 #pragma once
 
 #include "force_qp_coop.hpp"
+#include "kernarg_mirror.hpp" // the check of every struct read through kernel_arguments_again (below)
 #include "qlamd.h" // QLAMD_SET_MEMORY_SLOT
 
 namespace qlamd {

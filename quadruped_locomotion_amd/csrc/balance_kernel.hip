@@ -4,8 +4,6 @@
 #include "params_build.hpp"
 #include "context.hpp"
 
-#include <cstddef>
-#include <tuple>
 #include <type_traits>
 
 using namespace qlamd;
@@ -476,18 +474,6 @@ __device__ __forceinline__ void placement_wave(const int32_t *__restrict__ iters
 // function that is not a kernel has none of its own -- and keeps nothing else for it).
 // (BalanceCoopArgs mirrors the parameters of balance_coop_kernel by hand: the checks behind the kernel tie the two together)
 struct BalanceCoopArgs { const DeviceParams *Pp; StatePtrs s; int64_t B; double *tau, *grf; int32_t *status; }; // the kernel's parameters
-// Where a kernel's parameters lie in its argument segment: each at its natural alignment, in the order of the signature
-template <class F> struct KernargLayout;
-template <class... P> struct KernargLayout<void (*)(P...)> {
-  static constexpr size_t count = sizeof...(P);
-  static constexpr size_t offset(size_t k) { // (k == count: the length of the segment's explicit part)
-    const size_t size[] = {sizeof(P)...}, align[] = {alignof(P)...};
-    size_t o = 0;
-    for (size_t j = 0; j < k; j++) o = (o + align[j] - 1) / align[j] * align[j] + size[j];
-    return k < count ? (o + align[k] - 1) / align[k] * align[k] : o;
-  }
-  template <size_t k> using type = std::tuple_element_t<k, std::tuple<P...>>;
-};
 template <bool kPerLeg, int kMinWaves>
 __device__ __forceinline__ void cold_retry_body(const BalanceCoopArgs *args, double *lds, bool rejected) {
   const BalanceCoopArgs &a = *args;
@@ -570,14 +556,7 @@ __global__ __launch_bounds__(64 * kCoopWaves, kMinWaves) void balance_table_kern
 // balance_cold_retry reads the kernel's arguments through BalanceCoopArgs laid over the argument segment: same members, same
 // types, same places as the parameters of the kernels (every instantiation of the two has the one signature)
 using CoopKernelLayout = KernargLayout<decltype(&balance_coop_kernel<false, 2, true, true>)>;
-#define QL_ARG_MATCHES(k, member)                                                                                   \
-  static_assert(std::is_same<CoopKernelLayout::type<k>, decltype(BalanceCoopArgs::member)>::value &&                  \
-                    CoopKernelLayout::offset(k) == offsetof(BalanceCoopArgs, member),                               \
-                "BalanceCoopArgs::" #member " is not parameter " #k " of balance_coop_kernel")
-static_assert(CoopKernelLayout::count == 6, "balance_coop_kernel has grown a parameter: BalanceCoopArgs has to grow with it");
-QL_ARG_MATCHES(0, Pp); QL_ARG_MATCHES(1, s); QL_ARG_MATCHES(2, B); QL_ARG_MATCHES(3, tau); QL_ARG_MATCHES(4, grf); QL_ARG_MATCHES(5, status);
-#undef QL_ARG_MATCHES
-static_assert(CoopKernelLayout::offset(6) == sizeof(BalanceCoopArgs), "BalanceCoopArgs is not as long as the kernel's parameters");
+QL_KERNARG_MIRROR(CoopKernelLayout, BalanceCoopArgs, true, Pp, s, B, tau, grf, status);
 static_assert(std::is_same<decltype(&balance_coop_kernel<false, 2, true, true>), decltype(&balance_table_kernel<true, 3>)>::value,
               "balance_table_kernel takes the parameters of balance_coop_kernel");
 
@@ -893,9 +872,14 @@ int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, i
   // (prev_working_set == working_set is fine: a robot's set is read and written by its own 16 lanes only -- updated in place)
   const bool placed = pl.robot_order || pl.iterations || pl.next_robot_order || warm;
   const int policy = pl.next_robot_order ? effective_policy(pl.policy, batch, warm) : QLAMD_PLACEMENT_NONE;
-  StatePtrs s{in.joint_position, in.base_position, in.base_orientation, in.base_linear_velocity, in.base_angular_velocity,
-              in.desired_position, in.desired_orientation, in.desired_linear_velocity, in.desired_angular_velocity,
-              in.support_leg, in.surface_normal, wrench, live, support_only, pl.robot_order, pl.iterations, nullptr, nullptr, 0};
+  StatePtrs s{};
+  s.q = in.joint_position; s.pos = in.base_position; s.quat = in.base_orientation;
+  s.linvel = in.base_linear_velocity; s.angvel = in.base_angular_velocity;
+  s.dpos = in.desired_position; s.dquat = in.desired_orientation;
+  s.dlinvel = in.desired_linear_velocity; s.dangvel = in.desired_angular_velocity;
+  s.stance = in.support_leg; s.normals = in.surface_normal;
+  s.wrench = wrench; s.live = live; s.support_only = support_only;
+  s.order = pl.robot_order; s.iterations = pl.iterations;
   s.record_doubles = layout == QLAMD_STATE_RECORDS ? QLAMD_STATE_RECORD_DOUBLES : 0;
   s.prev_working_set = pl.prev_working_set;
   s.working_set = pl.working_set;
@@ -999,43 +983,30 @@ int balance_entry(qlamd_context *ctx, const qlamd_state_batch *in_user, const do
   if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
-  if (memory == QLAMD_MEM_DEVICE) {
-    // records instead of per-field arrays: the lane-cooperative kernels only (and never with an external wrench, whose entry
-    // points the unused pose fields at joint_position); host-buffer calls take per-field arrays whatever the option says
-    const int layout = ctx->state_record_doubles ? QLAMD_STATE_RECORDS : QLAMD_STATE_FIELDS;
-    if (layout == QLAMD_STATE_RECORDS && (pick_rpw(ctx, batch) != 4 || wrench)) return QLAMD_ERR_INVALID_ARGUMENT;
-    return balance_launch(ctx, in, layout, wrench, nullptr, 0, p, batch, joint_effort, contact_force, status, st);
-  }
+  // records instead of per-field arrays: the lane-cooperative kernels only (and never with an external wrench, whose entry
+  // points the unused pose fields at joint_position); host-buffer calls take per-field arrays whatever the option says
+  const int layout = memory == QLAMD_MEM_DEVICE && ctx->state_record_doubles ? QLAMD_STATE_RECORDS : QLAMD_STATE_FIELDS;
+  if (layout == QLAMD_STATE_RECORDS && (pick_rpw(ctx, batch) != 4 || wrench)) return QLAMD_ERR_INVALID_ARGUMENT;
+  qlamd_placement dp = p;
+  if (memory == QLAMD_MEM_HOST) dp.prev_iterations = dp.next_robot_order = nullptr; // made on the host, behind the launch
   // host buffers: inputs, then outputs.  QLAMD_ON_FAILURE_KEEP: a failed robot's entries are not written by the kernel, and
   // the outputs are copied back whole -- so the caller's efforts / forces go up with the inputs and come back untouched.
   // (with an external wrench the pose / twist fields alias the head of joint_position)
   const size_t B = (size_t)batch;
   const bool keep = ctx->params.keep_on_failure != 0;
-  Staged sg;
-  const int i_q = sg.add(in.joint_position, B * 96, true, false), i_pos = sg.add(in.base_position, B * 24, true, false);
-  const int i_quat = sg.add(in.base_orientation, B * 32, true, false), i_lin = sg.add(in.base_linear_velocity, B * 24, true, false);
-  const int i_ang = sg.add(in.base_angular_velocity, B * 24, true, false), i_dpos = sg.add(in.desired_position, B * 24, true, false);
-  const int i_dquat = sg.add(in.desired_orientation, B * 32, true, false);
-  const int i_dlin = sg.add(in.desired_linear_velocity, B * 24, true, false);
-  const int i_dang = sg.add(in.desired_angular_velocity, B * 24, true, false), i_sup = sg.add(in.support_leg, B * 4, true, false);
-  const int i_nrm = sg.add(in.surface_normal, B * 96, true, false), i_w = sg.add(wrench, B * 48, true, false);
-  const int i_ord = sg.add(p.robot_order, B * 4, true, false);
-  const int o_tau = sg.add(joint_effort, B * 96, keep, true), o_grf = sg.add(contact_force, B * 96, keep, true);
-  const int o_st = sg.add(status, B * 4, false, true), o_it = sg.add(p.iterations, B * 4, false, true);
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(in.joint_position, B * 96); sg.in(in.base_position, B * 24); sg.in(in.base_orientation, B * 32);
+  sg.in(in.base_linear_velocity, B * 24); sg.in(in.base_angular_velocity, B * 24);
+  sg.in(in.desired_position, B * 24); sg.in(in.desired_orientation, B * 32);
+  sg.in(in.desired_linear_velocity, B * 24); sg.in(in.desired_angular_velocity, B * 24);
+  sg.in(in.support_leg, B * 4); sg.in(in.surface_normal, B * 96); sg.in(wrench, B * 48); sg.in(dp.robot_order, B * 4);
+  sg.out(joint_effort, B * 96, keep); sg.out(contact_force, B * 96, keep);
+  sg.out(status, B * 4); sg.out(dp.iterations, B * 4);
   int rc = sg.upload(ctx, st);
   if (rc != QLAMD_OK) return rc;
-  const qlamd_state_batch d{sg.dev<const double>(i_q), sg.dev<const double>(i_pos), sg.dev<const double>(i_quat),
-                            sg.dev<const double>(i_lin), sg.dev<const double>(i_ang), sg.dev<const double>(i_dpos),
-                            sg.dev<const double>(i_dquat), sg.dev<const double>(i_dlin), sg.dev<const double>(i_dang),
-                            sg.dev<const uint8_t>(i_sup), sg.dev<const double>(i_nrm)};
-  qlamd_placement dp;
-  memset(&dp, 0, sizeof(dp));
-  dp.robot_order = sg.dev<const int32_t>(i_ord);
-  dp.iterations = sg.dev<int32_t>(o_it);
-  rc = balance_launch(ctx, d, QLAMD_STATE_FIELDS, sg.dev<const double>(i_w), nullptr, 0, dp, batch, sg.dev<double>(o_tau),
-                      sg.dev<double>(o_grf), sg.dev<int32_t>(o_st), st);
+  rc = balance_launch(ctx, in, layout, wrench, nullptr, 0, dp, batch, joint_effort, contact_force, status, st);
   if (rc == QLAMD_OK) rc = sg.finish(st);
-  if (rc == QLAMD_OK && p.next_robot_order)
+  if (rc == QLAMD_OK && memory == QLAMD_MEM_HOST && p.next_robot_order)
     rc = qlamd_placement_from_iterations(ctx, p.prev_iterations, batch, p.policy, p.next_robot_order, QLAMD_MEM_HOST, stream);
   return rc;
 }
@@ -1113,19 +1084,12 @@ int qlamd_placement_from_iterations(qlamd_context *ctx, const int32_t *iteration
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  const int32_t *d_it = iterations;
-  int32_t *d_ord = robot_order;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int a = sg.add(iterations, B * 4, true, false), o = sg.add(robot_order, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    d_it = sg.dev<const int32_t>(a);
-    d_ord = sg.dev<int32_t>(o);
-  }
-  const int rc = launch_placement(ctx, d_it, batch, throughput_policy(policy, batch) ? 1 : 0, d_ord, st);
-  if (rc != QLAMD_OK) return rc;
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(iterations, B * 4);
+  sg.out(robot_order, B * 4);
+  if (const int rc = sg.upload(ctx, st)) return rc;
+  if (const int rc = launch_placement(ctx, iterations, batch, throughput_policy(policy, batch) ? 1 : 0, robot_order, st)) return rc;
+  return sg.finish(st);
 }
 
 int qlamd_virtual_wrench_batch(qlamd_context *ctx, const qlamd_state_batch *in, int64_t batch, double *wrench,
@@ -1140,28 +1104,19 @@ int qlamd_virtual_wrench_batch(qlamd_context *ctx, const qlamd_state_batch *in, 
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  StatePtrs s{in->joint_position, in->base_position, in->base_orientation, in->base_linear_velocity,
-              in->base_angular_velocity, in->desired_position, in->desired_orientation,
-              in->desired_linear_velocity, in->desired_angular_velocity, in->support_leg, nullptr, nullptr, nullptr};
-  double *d_w = wrench;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int a1 = sg.add(in->base_position, B * 24, true, false), a2 = sg.add(in->base_orientation, B * 32, true, false);
-    const int a3 = sg.add(in->base_linear_velocity, B * 24, true, false), a4 = sg.add(in->base_angular_velocity, B * 24, true, false);
-    const int a5 = sg.add(in->desired_position, B * 24, true, false), a6 = sg.add(in->desired_orientation, B * 32, true, false);
-    const int a7 = sg.add(in->desired_linear_velocity, B * 24, true, false);
-    const int a8 = sg.add(in->desired_angular_velocity, B * 24, true, false), o = sg.add(wrench, B * 48, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s = StatePtrs{nullptr, sg.dev<const double>(a1), sg.dev<const double>(a2), sg.dev<const double>(a3),
-                  sg.dev<const double>(a4), sg.dev<const double>(a5), sg.dev<const double>(a6), sg.dev<const double>(a7),
-                  sg.dev<const double>(a8), nullptr, nullptr, nullptr, nullptr};
-    d_w = sg.dev<double>(o);
-  }
+  StatePtrs s{}; // only the base state enters the wrench (virtual_wrench_kernel)
+  s.pos = in->base_position; s.quat = in->base_orientation; s.linvel = in->base_linear_velocity;
+  s.angvel = in->base_angular_velocity; s.dpos = in->desired_position; s.dquat = in->desired_orientation;
+  s.dlinvel = in->desired_linear_velocity; s.dangvel = in->desired_angular_velocity;
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.pos, B * 24); sg.in(s.quat, B * 32); sg.in(s.linvel, B * 24); sg.in(s.angvel, B * 24);
+  sg.in(s.dpos, B * 24); sg.in(s.dquat, B * 32); sg.in(s.dlinvel, B * 24); sg.in(s.dangvel, B * 24);
+  sg.out(wrench, B * 48);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const unsigned grid = (unsigned)((batch + 63) / 64);
-  hipLaunchKernelGGL(virtual_wrench_kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, s, batch, d_w);
+  hipLaunchKernelGGL(virtual_wrench_kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, s, batch, wrench);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 int qlamd_leg_kinematics_batch(qlamd_context *ctx, const double *joint_position, const double *base_orientation,
@@ -1174,22 +1129,15 @@ int qlamd_leg_kinematics_batch(qlamd_context *ctx, const double *joint_position,
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  const double *d_q = joint_position, *d_quat = base_orientation;
-  double *d_f = foot_position, *d_j = jacobian, *d_g = gravity_torque;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int a1 = sg.add(joint_position, B * 96, true, false), a2 = sg.add(base_orientation, B * 32, true, false);
-    const int o1 = sg.add(foot_position, B * 96, false, true), o2 = sg.add(jacobian, B * 288, false, true);
-    const int o3 = sg.add(gravity_torque, B * 96, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    d_q = sg.dev<const double>(a1); d_quat = sg.dev<const double>(a2);
-    d_f = sg.dev<double>(o1); d_j = sg.dev<double>(o2); d_g = sg.dev<double>(o3);
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(joint_position, B * 96); sg.in(base_orientation, B * 32);
+  sg.out(foot_position, B * 96); sg.out(jacobian, B * 288); sg.out(gravity_torque, B * 96);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const unsigned grid = (unsigned)((4 * batch + 63) / 64);
-  hipLaunchKernelGGL(leg_kinematics_kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, d_q, d_quat, batch, d_f, d_j, d_g);
+  hipLaunchKernelGGL(leg_kinematics_kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, joint_position, base_orientation, batch,
+                     foot_position, jacobian, gravity_torque);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 } // extern "C"

@@ -265,7 +265,8 @@ __device__ __forceinline__ int64_t placed_index(const PlacePtrs &pp, int64_t slo
 // Returns QLAMD_OK and fills pp / *next (next->next_robot_order != NULL when a following placement was asked for), or
 // QLAMD_ERR_INVALID_ARGUMENT for a host-memory call (the placement's arrays are device arrays).
 inline int take_placement(qlamd_context *ctx, int memory, int64_t batch, PlacePtrs *pp, qlamd_placement *next) {
-  *pp = PlacePtrs{nullptr, nullptr, nullptr, nullptr, (uint32_t *)ctx->place_sync + kSyncWarmRetries};
+  *pp = PlacePtrs{};
+  pp->warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
   memset(next, 0, sizeof(*next));
   if (!ctx->has_next_placement) return QLAMD_OK;
   const qlamd_placement pl = ctx->next_placement;
@@ -314,38 +315,32 @@ inline int ensure_pinned(qlamd_context *ctx, size_t bytes) {
 }
 constexpr size_t kSmallHostCall = 256 * 1024; // below this a host-buffer call goes through one pinned slab
 
-// Host-buffer calls: the listed arrays are laid out in the context workspace, inputs copied up front,
-// outputs copied back (and the stream synchronised) by finish().  Calls whose arrays total at most
-// kSmallHostCall bytes go through the context's pinned slab: one copy up (the span of the inputs) and
-// one copy down (the span of the outputs) instead of one pageable copy per array.
-struct Staged {
-  struct Item { void *host; size_t bytes; bool in, out; size_t off; };
-  static constexpr int kMaxItems = 24;
-  Item items[kMaxItems];
-  int n = 0;
-  bool full = false;    // more than kMaxItems arrays were added (upload() refuses the call)
-  char *base = nullptr;
-  char *slab = nullptr; // pinned mirror of the workspace for small calls
-  int add(const void *host, size_t bytes, bool in, bool out) {
-    if (n == kMaxItems) { full = true; return n - 1; }
-    items[n] = Item{const_cast<void *>(host), host ? bytes : 0, in, out, 0};
-    return n++;
-  }
-  void span(bool want_out, size_t *lo, size_t *hi) const {
-    *lo = ~(size_t)0; *hi = 0;
-    for (int k = 0; k < n; k++) {
-      if (!items[k].bytes || !(want_out ? items[k].out : items[k].in)) continue;
-      if (items[k].off < *lo) *lo = items[k].off;
-      if (items[k].off + items[k].bytes > *hi) *hi = items[k].off + items[k].bytes;
-    }
-  }
+// Host-buffer calls.  An entry binds each of its pointer VARIABLES once, inputs first, outputs after: in() / out() / inout()
+// note the variable and the bytes behind it, upload() lays the arrays out in the context workspace in the order they were
+// bound, copies the inputs up and points every bound variable at its staged array (a NULL pointer stays NULL and stages
+// nothing), finish() copies the outputs back and synchronises the stream.  Calls whose arrays total at most kSmallHostCall
+// bytes go through the context's pinned slab: one copy up (the span of the inputs) and one copy down (the span of the
+// outputs) instead of one pageable copy per array.  For a device-memory call (host_call false) every method does nothing
+// and returns QLAMD_OK: the variables keep the caller's pointers.
+class Staged {
+ public:
+  static constexpr int kMaxItems = 24; // upload() refuses a call that binds more
+  explicit Staged(bool host_call) : on(host_call) {}
+  template <class T> void in(const T *&p, size_t bytes) { bind(p, 0, bytes, true, false); }
+  template <class T> void out(T *&p, size_t bytes, bool also_in = false) { bind(p, 0, bytes, also_in, true); }
+  template <class T> void inout(T *&p, size_t bytes) { bind(p, 0, bytes, true, true); }
+  // an input the kernel indexes from `bias` elements on: p[bias] ... are staged, and p is pointed `bias` elements in front of them
+  template <class T> void in_biased(const T *&p, int64_t bias, size_t bytes) { bind(p, bias * (int64_t)sizeof(T), bytes, true, false); }
   int upload(qlamd_context *ctx, hipStream_t st) {
+    if (!on) return QLAMD_OK;
     if (full) return QLAMD_ERR_INVALID_ARGUMENT;
     size_t total = 0;
     for (int k = 0; k < n; k++) { items[k].off = total; total += align256(items[k].bytes); }
     int rc = ensure_ws(ctx, total ? total : 256);
     if (rc != QLAMD_OK) return rc;
     base = (char *)ctx->ws;
+    for (int k = 0; k < n; k++)
+      if (items[k].host) items[k].point(items[k].var, base + items[k].off - items[k].bias);
     if (total && total <= kSmallHostCall) {
       rc = ensure_pinned(ctx, kSmallHostCall);
       if (rc != QLAMD_OK) return rc;
@@ -364,8 +359,8 @@ struct Staged {
         return QLAMD_ERR_HIP;
     return QLAMD_OK;
   }
-  template <class T> T *dev(int k) const { return items[k].host ? (T *)(base + items[k].off) : nullptr; }
   int finish(hipStream_t st) {
+    if (!on) return QLAMD_OK;
     if (slab) {
       size_t lo, hi;
       span(true, &lo, &hi);
@@ -381,6 +376,29 @@ struct Staged {
           hipMemcpyAsync(items[k].host, base + items[k].off, items[k].bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
         return QLAMD_ERR_HIP;
     return hipStreamSynchronize(st) == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
+  }
+
+ private:
+  // var: the bound variable, written through point() with its own type; host: the first staged byte (NULL: nothing staged)
+  struct Item { void *var; void (*point)(void *var, char *to); char *host; int64_t bias; size_t bytes; bool in, out; size_t off; };
+  Item items[kMaxItems];
+  int n = 0;
+  bool on, full = false;
+  char *base = nullptr;
+  char *slab = nullptr; // pinned mirror of the workspace for small calls
+  template <class P> void bind(P *&var, int64_t bias, size_t bytes, bool in, bool out) {
+    if (!on) return;
+    if (n == kMaxItems) { full = true; return; }
+    char *host = var ? (char *)var + bias : nullptr;
+    items[n++] = Item{&var, [](void *v, char *to) { *static_cast<P **>(v) = (P *)to; }, host, bias, host ? bytes : 0, in, out, 0};
+  }
+  void span(bool want_out, size_t *lo, size_t *hi) const {
+    *lo = ~(size_t)0; *hi = 0;
+    for (int k = 0; k < n; k++) {
+      if (!items[k].bytes || !(want_out ? items[k].out : items[k].in)) continue;
+      if (items[k].off < *lo) *lo = items[k].off;
+      if (items[k].off + items[k].bytes > *hi) *hi = items[k].off + items[k].bytes;
+    }
   }
 };
 

@@ -483,24 +483,12 @@ static int pose_impl(const PoseCall &call, qlamd_context *ctx, const qlamd_pose_
   int32_t *d_it = call.iterations, *d_st = call.status, *d_stage = call.stage;
   const double *d_min = call.min_len, *d_sfo = call.sfo;
   uint8_t *d_ok = call.ok;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int i_st = sg.add(in->stance, B * 96, true, false), i_nom = sg.add(in->nominal_stance, B * 96, true, false);
-    const int i_poly = sg.add(in->support_polygon, B * 64, true, false), i_com = sg.add(in->center_of_mass, B * 24, true, false);
-    const int i_len = sg.add(in->max_limb_length, B * 32, true, false), i_pose = sg.add(in->pose, B * 56, true, false);
-    const int i_mask = sg.add(in->stance_mask, B * 4, true, false), i_nv = sg.add(in->n_vertices, B * 4, true, false);
-    const int i_min = sg.add(call.min_len, B * 32, true, false), i_sfo = sg.add(call.sfo, B * 96, true, false);
-    const int o_out = sg.add(call.pose_out, B * 56, false, true), o_it = sg.add(call.iterations, B * 4, false, true);
-    const int o_st = sg.add(call.status, B * 4, false, true), o_stage = sg.add(call.stage, B * 4, false, true);
-    const int o_ok = sg.add(call.ok, B, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s = PosePtrs{sg.dev<const double>(i_st), sg.dev<const double>(i_nom), sg.dev<const double>(i_poly), sg.dev<const double>(i_com),
-                 sg.dev<const double>(i_len), sg.dev<const double>(i_pose), sg.dev<const uint8_t>(i_mask), sg.dev<const int32_t>(i_nv)};
-    d_min = sg.dev<const double>(i_min); d_sfo = sg.dev<const double>(i_sfo);
-    d_out = sg.dev<double>(o_out); d_it = sg.dev<int32_t>(o_it); d_st = sg.dev<int32_t>(o_st); d_stage = sg.dev<int32_t>(o_stage);
-    d_ok = sg.dev<uint8_t>(o_ok);
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.stance, B * 96); sg.in(s.nominal, B * 96); sg.in(s.polygon, B * 64); sg.in(s.rcom, B * 24);
+  sg.in(s.maxlen, B * 32); sg.in(s.pose, B * 56); sg.in(s.mask, B * 4); sg.in(s.nverts, B * 4);
+  sg.in(d_min, B * 32); sg.in(d_sfo, B * 96);
+  sg.out(d_out, B * 56); sg.out(d_it, B * 4); sg.out(d_st, B * 4); sg.out(d_stage, B * 4); sg.out(d_ok, B);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const unsigned rgrid = (unsigned)((batch + coop::kPoseCoopRows - 1) / coop::kPoseCoopRows); // 4 problems per wavefront
   switch (mode) {
     case kPoseSqp:
@@ -522,7 +510,7 @@ static int pose_impl(const PoseCall &call, qlamd_context *ctx, const qlamd_pose_
       break;
   }
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 int qlamd_pose_sqp_batch(qlamd_context *ctx, const qlamd_pose_params *params, const qlamd_pose_batch *in,
@@ -583,25 +571,15 @@ int qlamd_qp_solve_batch(qlamd_context *ctx, int n, int p, int m, const double *
   { const int rc = take_placement(ctx, memory, batch, &pp, &pl); if (rc != QLAMD_OK) return rc; }
   if (pp.prev_working_set || pp.working_set) return QLAMD_ERR_INVALID_ARGUMENT; // (the dense entries start cold)
   const size_t B = (size_t)batch;
-  const double *dG = G, *dg0 = g0, *dCE = CE, *dce0 = ce0, *dCI = CI, *dci0 = ci0;
-  double *dx = x, *dobj = objective;
-  int32_t *dst = status;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int iG = sg.add(G, B * n * n * 8, true, false), ig = sg.add(g0, B * n * 8, true, false);
-    const int iCE = sg.add(CE, B * n * p * 8, true, false), ice = sg.add(ce0, B * p * 8, true, false);
-    const int iCI = sg.add(CI, B * n * m * 8, true, false), ici = sg.add(ci0, B * m * 8, true, false);
-    const int ox = sg.add(x, B * n * 8, false, true), oo = sg.add(objective, B * 8, false, true), os = sg.add(status, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    dG = sg.dev<const double>(iG); dg0 = sg.dev<const double>(ig); dCE = sg.dev<const double>(iCE);
-    dce0 = sg.dev<const double>(ice); dCI = sg.dev<const double>(iCI); dci0 = sg.dev<const double>(ici);
-    dx = sg.dev<double>(ox); dobj = sg.dev<double>(oo); dst = sg.dev<int32_t>(os);
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(G, B * n * n * 8); sg.in(g0, B * n * 8); sg.in(CE, B * n * p * 8); sg.in(ce0, B * p * 8);
+  sg.in(CI, B * n * m * 8); sg.in(ci0, B * m * 8);
+  sg.out(x, B * n * 8); sg.out(objective, B * 8); sg.out(status, B * 4);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   {
     const unsigned cgrid = (unsigned)((batch + coop::kQpCoopRows - 1) / coop::kQpCoopRows);
     auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(cgrid), dim3(64), 0, st, n, p, m, dG, dg0, dCE, dce0, dCI, dci0, batch, dx, dobj, dst, pp);
+      hipLaunchKernelGGL(kern, dim3(cgrid), dim3(64), 0, st, n, p, m, G, g0, CE, ce0, CI, ci0, batch, x, objective, status, pp);
     };
     if (m > 24) {
       if (n <= 6) launch(qp_coop_kernel<6, 3>); else launch(qp_coop_kernel<12, 3>);
@@ -611,7 +589,7 @@ int qlamd_qp_solve_batch(qlamd_context *ctx, int n, int p, int m, const double *
   }
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   { const int rc = finish_placement(ctx, pl, batch, st); if (rc != QLAMD_OK) return rc; }
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 int qlamd_weighted_lsq_qp_batch(qlamd_context *ctx, int n, int k, int p, int m, const double *A, const double *S,
@@ -631,30 +609,21 @@ int qlamd_weighted_lsq_qp_batch(qlamd_context *ctx, int n, int k, int p, int m, 
   { const int rc = take_placement(ctx, memory, batch, &pp, &pl); if (rc != QLAMD_OK) return rc; }
   if (pp.prev_working_set || pp.working_set) return QLAMD_ERR_INVALID_ARGUMENT; // (the dense entries start cold)
   const size_t B = (size_t)batch;
-  const double *dA = A, *dS = S, *db = b, *dW = W, *dC = p ? C : nullptr, *dc = p ? c : nullptr, *dD = m ? D : nullptr,
-               *dd = m ? d : nullptr, *df = m ? f : nullptr;
-  double *dx = x;
-  int32_t *dst = status;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int iA = sg.add(A, B * k * n * 8, true, false), iS = sg.add(S, B * k * 8, true, false), ib = sg.add(b, B * k * 8, true, false);
-    const int iW = sg.add(W, B * n * 8, true, false), iC = sg.add(dC, B * p * n * 8, true, false), ic = sg.add(dc, B * p * 8, true, false);
-    const int iD = sg.add(dD, B * m * n * 8, true, false), id = sg.add(dd, B * m * 8, true, false), iF = sg.add(df, B * m * 8, true, false);
-    const int ox = sg.add(x, B * n * 8, false, true), os = sg.add(status, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    dA = sg.dev<const double>(iA); dS = sg.dev<const double>(iS); db = sg.dev<const double>(ib); dW = sg.dev<const double>(iW);
-    dC = sg.dev<const double>(iC); dc = sg.dev<const double>(ic); dD = sg.dev<const double>(iD); dd = sg.dev<const double>(id);
-    df = sg.dev<const double>(iF); dx = sg.dev<double>(ox); dst = sg.dev<int32_t>(os);
-  }
+  if (!p) C = c = nullptr;
+  if (!m) D = d = f = nullptr;
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(A, B * k * n * 8); sg.in(S, B * k * 8); sg.in(b, B * k * 8); sg.in(W, B * n * 8); sg.in(C, B * p * n * 8);
+  sg.in(c, B * p * 8); sg.in(D, B * m * n * 8); sg.in(d, B * m * 8); sg.in(f, B * m * 8);
+  sg.out(x, B * n * 8); sg.out(status, B * 4);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const unsigned grid = (unsigned)((batch + coop::kQpCoopRows - 1) / coop::kQpCoopRows);
   if (n <= 6)
-    hipLaunchKernelGGL(weighted_lsq_qp_kernel<6>, dim3(grid), dim3(64), 0, st, n, k, p, m, dA, dS, db, dW, dC, dc, dD, dd, df, batch, dx, dst, pp);
+    hipLaunchKernelGGL(weighted_lsq_qp_kernel<6>, dim3(grid), dim3(64), 0, st, n, k, p, m, A, S, b, W, C, c, D, d, f, batch, x, status, pp);
   else
-    hipLaunchKernelGGL(weighted_lsq_qp_kernel<12>, dim3(grid), dim3(64), 0, st, n, k, p, m, dA, dS, db, dW, dC, dc, dD, dd, df, batch, dx, dst, pp);
+    hipLaunchKernelGGL(weighted_lsq_qp_kernel<12>, dim3(grid), dim3(64), 0, st, n, k, p, m, A, S, b, W, C, c, D, d, f, batch, x, status, pp);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   { const int rc = finish_placement(ctx, pl, batch, st); if (rc != QLAMD_OK) return rc; }
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 } // extern "C"

@@ -170,6 +170,9 @@ __global__ __launch_bounds__(64, 2) void tick_solve_kernel(const DeviceParams *_
   QL_BLOCK_STAMP(3);
 }
 
+using TickSolveLayout = KernargLayout<decltype(&tick_solve_kernel<true>)>;
+QL_KERNARG_MIRROR(TickSolveLayout, TickSolveArgs, false, Pp, cp, B, effort, status); // (a prefix: the swing blocks' arguments follow)
+
 // ---- leg state machine (row f2): one robot per lane, flags and a few doubles in, flags out ----------
 struct LegStatePtrs {
   const uint8_t *support_leg, *is_footstep, *contact;
@@ -758,6 +761,26 @@ __global__ __launch_bounds__(64) void robot_state_unpack_kernel(const uint8_t *_
   QL_BLOCK_STAMP(1);
 }
 
+using UnpackLayout = KernargLayout<decltype(&robot_state_unpack_kernel)>;
+QL_KERNARG_MIRROR(UnpackLayout, UnpackArgs, true, messages, offsets, B, o, status, tpl_in, tpl_out, valid, ls, leg_state_mode, window_bytes);
+
+// the public parameter structs as the kernels take them
+SwingParamsDev swing_params_dev(const qlamd_swing_params &p) {
+  SwingParamsDev SP;
+  for (int i = 0; i < 3; i++) { SP.kp[i] = p.kp[i]; SP.kd[i] = p.kd[i]; }
+  SP.period = p.period; SP.accel_window = p.accel_window; SP.accel_scale = p.accel_scale;
+  SP.gravity = p.gravity;
+  return SP;
+}
+PidParamsDev pid_params_dev(const qlamd_joint_pid_params &p) {
+  PidParamsDev PD;
+  memcpy(PD.p, p.p, sizeof(PD.p)); memcpy(PD.i, p.i, sizeof(PD.i)); memcpy(PD.d, p.d, sizeof(PD.d));
+  memcpy(PD.i_max, p.i_max, sizeof(PD.i_max)); memcpy(PD.i_min, p.i_min, sizeof(PD.i_min));
+  memcpy(PD.lower, p.lower, sizeof(PD.lower)); memcpy(PD.upper, p.upper, sizeof(PD.upper));
+  PD.antiwindup = p.antiwindup;
+  return PD;
+}
+
 } // namespace
 
 extern "C" {
@@ -785,34 +808,18 @@ int qlamd_swing_leg_torque_batch(qlamd_context *ctx, const qlamd_swing_params *p
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  SwingParamsDev SP;
-  for (int i = 0; i < 3; i++) { SP.kp[i] = params->kp[i]; SP.kd[i] = params->kd[i]; }
-  SP.period = params->period; SP.accel_window = params->accel_window; SP.accel_scale = params->accel_scale;
-  SP.gravity = params->gravity;
+  const SwingParamsDev SP = swing_params_dev(*params);
   SwingPtrs s{in->joint_position, in->joint_velocity, in->joint_velocity_oldest, in->target_foot_position,
               in->target_foot_velocity, in->id_joint_position, in->support_leg};
-  double *d_tau = joint_effort;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    sg.add(in->joint_position, B * 96, true, false);
-    sg.add(in->joint_velocity, B * 96, true, false);
-    sg.add(in->joint_velocity_oldest, B * 96, true, false);
-    sg.add(in->target_foot_position, B * 96, true, false);
-    sg.add(in->target_foot_velocity, B * 96, true, false);
-    sg.add(in->id_joint_position, B * 96, true, false);
-    sg.add(in->support_leg, B * 4, true, false);
-    sg.add(joint_effort, B * 96, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s = SwingPtrs{sg.dev<const double>(0), sg.dev<const double>(1), sg.dev<const double>(2), sg.dev<const double>(3),
-                  sg.dev<const double>(4), sg.dev<const double>(5), sg.dev<const uint8_t>(6)};
-    d_tau = sg.dev<double>(7);
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.q, B * 96); sg.in(s.qd, B * 96); sg.in(s.qd_old, B * 96); sg.in(s.tpos, B * 96); sg.in(s.tvel, B * 96);
+  sg.in(s.q_id, B * 96); sg.in(s.support, B * 4);
+  sg.out(joint_effort, B * 96);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const unsigned grid = (unsigned)((4 * batch + 63) / 64);
-  hipLaunchKernelGGL(swing_leg_kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, SP, s, batch, d_tau);
+  hipLaunchKernelGGL(swing_leg_kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, SP, s, batch, joint_effort);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  if (memory == QLAMD_MEM_HOST) return sg.finish(st);
-  return QLAMD_OK;
+  return sg.finish(st);
 }
 
 void qlamd_joint_pid_default_params(qlamd_joint_pid_params *p) {
@@ -844,43 +851,23 @@ static int swing_branch_impl(qlamd_context *ctx, const qlamd_swing_params *param
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  SwingParamsDev SP;
-  for (int i = 0; i < 3; i++) { SP.kp[i] = params->kp[i]; SP.kd[i] = params->kd[i]; }
-  SP.period = params->period; SP.accel_window = params->accel_window; SP.accel_scale = params->accel_scale;
-  SP.gravity = params->gravity;
-  PidParamsDev PD;
-  memcpy(PD.p, pid->p, sizeof(PD.p)); memcpy(PD.i, pid->i, sizeof(PD.i)); memcpy(PD.d, pid->d, sizeof(PD.d));
-  memcpy(PD.i_max, pid->i_max, sizeof(PD.i_max)); memcpy(PD.i_min, pid->i_min, sizeof(PD.i_min));
-  memcpy(PD.lower, pid->lower, sizeof(PD.lower)); memcpy(PD.upper, pid->upper, sizeof(PD.upper));
-  PD.antiwindup = pid->antiwindup;
+  const SwingParamsDev SP = swing_params_dev(*params);
+  const PidParamsDev PD = pid_params_dev(*pid);
   SwingPtrs s{in->joint_position, in->joint_velocity, in->joint_velocity_oldest, in->target_foot_position,
               in->target_foot_velocity, in->id_joint_position, in->support_leg};
   SwingBranchPtrs sb{extra->base_orientation, extra->joint_command, extra->leg_mode, extra->pid_error_last,
                      extra->pid_error_integral, live};
-  double *d_eff = joint_effort;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int a0 = sg.add(in->joint_position, B * 96, true, false), a1 = sg.add(in->joint_velocity, B * 96, true, false);
-    const int a2 = sg.add(in->joint_velocity_oldest, B * 96, true, false);
-    const int a3 = sg.add(in->target_foot_position, B * 96, true, false);
-    const int a4 = sg.add(in->target_foot_velocity, B * 96, true, false);
-    const int a5 = sg.add(in->id_joint_position, B * 96, true, false), a6 = sg.add(in->support_leg, B * 4, true, false);
-    const int b0 = sg.add(extra->base_orientation, B * 32, true, false), b1 = sg.add(extra->joint_command, B * 96, true, false);
-    const int b2 = sg.add(extra->leg_mode, B * 4, true, false);
-    const int b3 = sg.add(extra->pid_error_last, B * 96, true, true), b4 = sg.add(extra->pid_error_integral, B * 96, true, true);
-    const int e0 = sg.add(joint_effort, B * 96, true, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s = SwingPtrs{sg.dev<const double>(a0), sg.dev<const double>(a1), sg.dev<const double>(a2), sg.dev<const double>(a3),
-                  sg.dev<const double>(a4), sg.dev<const double>(a5), sg.dev<const uint8_t>(a6)};
-    sb = SwingBranchPtrs{sg.dev<const double>(b0), sg.dev<const double>(b1), sg.dev<const uint8_t>(b2), sg.dev<double>(b3),
-                         sg.dev<double>(b4), nullptr};
-    d_eff = sg.dev<double>(e0);
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.q, B * 96); sg.in(s.qd, B * 96); sg.in(s.qd_old, B * 96); sg.in(s.tpos, B * 96); sg.in(s.tvel, B * 96);
+  sg.in(s.q_id, B * 96); sg.in(s.support, B * 4);
+  sg.in(sb.quat, B * 32); sg.in(sb.cmd, B * 96); sg.in(sb.mode, B * 4);
+  sg.inout(sb.e_last, B * 96); sg.inout(sb.e_int, B * 96);
+  sg.inout(joint_effort, B * 96);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   hipLaunchKernelGGL(swing_branch_kernel, dim3((unsigned)((4 * batch + 63) / 64)), dim3(64), 0, st, ctx->d_params, SP, PD,
-                     s, sb, period, batch, d_eff);
+                     s, sb, period, batch, joint_effort);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 extern "C" {
@@ -904,34 +891,22 @@ int qlamd_leg_state_machine_batch(qlamd_context *ctx, const qlamd_leg_state_batc
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  LegStatePtrs s{io->support_leg, io->is_footstep, io->contact, io->phase, io->joint_position, io->limb_state,
-                 io->store_flag, io->stored_joint_position, io->joint_command, io->foot_target, io->support,
-                 io->leg_state_code, nullptr, nullptr, nullptr, nullptr};
+  LegStatePtrs s{}; // (the whole tick's members stay NULL)
+  s.support_leg = io->support_leg; s.is_footstep = io->is_footstep; s.contact = io->contact; s.phase = io->phase;
+  s.joint_position = io->joint_position; s.limb_state = io->limb_state; s.store_flag = io->store_flag;
+  s.stored_joint_position = io->stored_joint_position; s.joint_command = io->joint_command; s.foot_target = io->foot_target;
+  s.support = io->support; s.code = io->leg_state_code;
   // host staging: every array goes up except leg_state_code; the in/out and out arrays come back
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    sg.add(io->support_leg, B * 4, true, false);
-    sg.add(io->is_footstep, B * 4, true, false);
-    sg.add(io->contact, B * 4, true, false);
-    sg.add(io->phase, B * 32, true, false);
-    sg.add(io->joint_position, B * 96, true, false);
-    sg.add(io->limb_state, B * 4, true, true);
-    sg.add(io->store_flag, B * 4, true, true);
-    sg.add(io->stored_joint_position, B * 96, true, true);
-    sg.add(io->joint_command, B * 96, true, true);
-    sg.add(io->foot_target, B * 96, true, true);
-    sg.add(io->support, B * 4, true, true);
-    sg.add(io->leg_state_code, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s = LegStatePtrs{sg.dev<const uint8_t>(0), sg.dev<const uint8_t>(1), sg.dev<const uint8_t>(2), sg.dev<const double>(3),
-                     sg.dev<const double>(4), sg.dev<int8_t>(5), sg.dev<uint8_t>(6), sg.dev<double>(7), sg.dev<double>(8),
-                     sg.dev<double>(9), sg.dev<uint8_t>(10), sg.dev<int8_t>(11), nullptr, nullptr, nullptr, nullptr};
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.support_leg, B * 4); sg.in(s.is_footstep, B * 4); sg.in(s.contact, B * 4); sg.in(s.phase, B * 32);
+  sg.in(s.joint_position, B * 96);
+  sg.inout(s.limb_state, B * 4); sg.inout(s.store_flag, B * 4); sg.inout(s.stored_joint_position, B * 96);
+  sg.inout(s.joint_command, B * 96); sg.inout(s.foot_target, B * 96); sg.inout(s.support, B * 4);
+  sg.out(s.code, B * 4);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   hipLaunchKernelGGL(leg_state_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, s, index_quirk, batch);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  if (memory == QLAMD_MEM_HOST) return sg.finish(st);
-  return QLAMD_OK;
+  return sg.finish(st);
 }
 
 } // extern "C"
@@ -947,38 +922,24 @@ static int unpack_impl(qlamd_context *ctx, const uint8_t *messages, const int64_
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  enum { kD = 10 };
-  const int width[kD] = {3, 4, 3, 3, 12, 12, 12, 12, 12, 4};
-  double *hostd[kD] = {out->des_pos, out->des_quat, out->des_linvel, out->des_angvel, out->joint_command,
-                       out->foot_position, out->foot_velocity, out->foot_acceleration, out->surface_normal, out->phase};
   RobotStateOutPtrs o{out->des_pos, out->des_quat, out->des_linvel, out->des_angvel, out->joint_command,
                       out->foot_position, out->foot_velocity, out->foot_acceleration, out->surface_normal, out->phase,
                       out->support_leg, out->leg_mode};
-  const uint8_t *d_msg = messages;
-  const int64_t *d_off = offsets;
-  int32_t *d_st = status;
-  Staged sg;
+  const int64_t *const host_offsets = offsets; // (read by the host below; `offsets` is what the kernel gets)
+  Staged sg(memory == QLAMD_MEM_HOST);
   if (memory == QLAMD_MEM_HOST) {
     for (size_t k = 0; k < B; k++)
       if (offsets[k + 1] < offsets[k] || offsets[0] < 0) return QLAMD_ERR_INVALID_ARGUMENT;
-    const size_t nbytes = (size_t)(offsets[B] - offsets[0]);
     // inputs first, outputs after them: a small call is then one copy each way over a tight span
-    const int i_off = sg.add(offsets, (B + 1) * 8, true, false);
-    const int i_msg = sg.add(messages + offsets[0], nbytes, true, false);
-    int i_d[kD];
-    for (int k = 0; k < kD; k++) i_d[k] = sg.add(hostd[k], B * 8 * (size_t)width[k], false, true);
-    const int i_sup = sg.add(out->support_leg, B * 4, false, true);
-    const int i_mode = sg.add(out->leg_mode, B * 4, false, true);
-    const int i_st = sg.add(status, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    o = RobotStateOutPtrs{sg.dev<double>(i_d[0]), sg.dev<double>(i_d[1]), sg.dev<double>(i_d[2]), sg.dev<double>(i_d[3]),
-                          sg.dev<double>(i_d[4]), sg.dev<double>(i_d[5]), sg.dev<double>(i_d[6]), sg.dev<double>(i_d[7]),
-                          sg.dev<double>(i_d[8]), sg.dev<double>(i_d[9]), sg.dev<uint8_t>(i_sup), sg.dev<uint8_t>(i_mode)};
-    d_st = sg.dev<int32_t>(i_st);
-    d_off = sg.dev<const int64_t>(i_off);
-    d_msg = (const uint8_t *)(sg.base + sg.items[i_msg].off) - offsets[0]; // the kernel indexes with the caller's offsets
+    sg.in(offsets, (B + 1) * 8);
+    sg.in_biased(messages, host_offsets[0], (size_t)(host_offsets[B] - host_offsets[0])); // the kernel indexes with the caller's offsets
+    sg.out(o.des_pos, B * 24); sg.out(o.des_quat, B * 32); sg.out(o.des_linvel, B * 24); sg.out(o.des_angvel, B * 24);
+    sg.out(o.joint_command, B * 96); sg.out(o.foot_position, B * 96); sg.out(o.foot_velocity, B * 96);
+    sg.out(o.foot_acceleration, B * 96); sg.out(o.surface_normal, B * 96); sg.out(o.phase, B * 32);
+    sg.out(o.support_leg, B * 4); sg.out(o.leg_mode, B * 4);
+    sg.out(status, B * 4);
   }
+  if (const int rc = sg.upload(ctx, st)) return rc;
   if (!ctx->wire_tpl) { // zero = "no template yet": the first launch walks every message
     if (rt::CallGuard::capturing(st)) return QLAMD_ERR_NEEDS_RESERVE;
     if (hipMalloc((void **)&ctx->wire_tpl, 2 * kTplWords * sizeof(uint32_t)) != hipSuccess) return QLAMD_ERR_OUT_OF_MEMORY;
@@ -999,15 +960,14 @@ static int unpack_impl(qlamd_context *ctx, const uint8_t *messages, const int64_
     window = kWireLdsBytesSmall;
     for (int64_t i = 0; i < batch && window == kWireLdsBytesSmall; i += kWireMsgsPerBlock) {
       const int64_t j = i + kWireMsgsPerBlock < batch ? i + kWireMsgsPerBlock : batch;
-      if (offsets[j] - offsets[i] + 32 > kWireLdsBytesSmall) window = kWireLdsBytes; // (+16 of alignment lead, +16 of overread)
+      if (host_offsets[j] - host_offsets[i] + 32 > kWireLdsBytesSmall) window = kWireLdsBytes; // (+16 of alignment lead, +16 of overread)
     }
   }
   hipLaunchKernelGGL(robot_state_unpack_kernel, dim3((unsigned)((batch + kWireMsgsPerBlock - 1) / kWireMsgsPerBlock)),
-                     dim3(64), window, st, d_msg, d_off, batch, o, d_st, tpl_in, tpl_out, valid,
+                     dim3(64), window, st, messages, offsets, batch, o, status, tpl_in, tpl_out, valid,
                      ls ? *ls : LegStatePtrs{}, ls ? leg_state_mode : 0, window);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  if (memory == QLAMD_MEM_HOST) return sg.finish(st);
-  return QLAMD_OK;
+  return sg.finish(st);
 }
 
 extern "C" {
@@ -1042,21 +1002,14 @@ int qlamd_leg_inverse_kinematics_batch(qlamd_context *ctx, const qlamd_ik_params
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  const double *d_foot = foot_position, *d_last = joint_position_last;
-  double *d_q = joint_position;
-  uint8_t *d_ok = ok;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    const int a = sg.add(foot_position, B * 96, true, false), b2 = sg.add(joint_position_last, B * 96, true, false);
-    const int c = sg.add(joint_position, B * 96, false, true), d = sg.add(ok, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    d_foot = sg.dev<const double>(a); d_last = sg.dev<const double>(b2); d_q = sg.dev<double>(c); d_ok = sg.dev<uint8_t>(d);
-  }
-  hipLaunchKernelGGL(leg_ik_kernel, dim3((unsigned)((4 * batch + 63) / 64)), dim3(64), 0, st, ctx->d_params, G, d_foot,
-                     d_last, batch, d_q, d_ok);
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(foot_position, B * 96); sg.in(joint_position_last, B * 96);
+  sg.out(joint_position, B * 96); sg.out(ok, B * 4);
+  if (const int rc = sg.upload(ctx, st)) return rc;
+  hipLaunchKernelGGL(leg_ik_kernel, dim3((unsigned)((4 * batch + 63) / 64)), dim3(64), 0, st, ctx->d_params, G, foot_position,
+                     joint_position_last, batch, joint_position, ok);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  return memory == QLAMD_MEM_HOST ? sg.finish(st) : QLAMD_OK;
+  return sg.finish(st);
 }
 
 // Layout of the command block of the whole tick (qlamd_tick_batch.command): per-robot flag "a command is in force",
@@ -1125,43 +1078,24 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
   size_t coff[kCmdN];
   const size_t cmd_bytes = command_layout(B, coff);
   qlamd_tick_batch d = *io;
-  Staged sg;
+  Staged sg(memory == QLAMD_MEM_HOST);
   if (memory == QLAMD_MEM_HOST) {
     for (size_t k = 0; k < B; k++)
       if (io->offsets[k + 1] < io->offsets[k] || io->offsets[0] < 0) return QLAMD_ERR_INVALID_ARGUMENT;
-    const size_t nbytes = (size_t)(io->offsets[B] - io->offsets[0]);
-    const int i_off = sg.add(io->offsets, (B + 1) * 8, true, false);
-    const int i_msg = sg.add(io->messages + io->offsets[0], nbytes, true, false); // an empty blob stages nothing
-    const int i_in[8] = {sg.add(io->joint_position, B * 96, true, false), sg.add(io->joint_velocity, B * 96, true, false),
-                         sg.add(io->joint_velocity_oldest, B * 96, true, false), sg.add(io->base_position, B * 24, true, false),
-                         sg.add(io->base_orientation, B * 32, true, false), sg.add(io->base_linear_velocity, B * 24, true, false),
-                         sg.add(io->base_angular_velocity, B * 24, true, false), sg.add(io->contact, B * 4, true, false)};
-    const int i_io[7] = {sg.add(io->limb_state, B * 4, true, true), sg.add(io->store_flag, B * 4, true, true),
-                         sg.add(io->stored_joint_position, B * 96, true, true), sg.add(io->leg_mode, B * 4, true, true),
-                         sg.add(io->pid_error_last, B * 96, true, true), sg.add(io->pid_error_integral, B * 96, true, true),
-                         sg.add(io->support, B * 4, true, true)};
+    sg.in(d.offsets, (B + 1) * 8);
+    sg.in_biased(d.messages, io->offsets[0], (size_t)(io->offsets[B] - io->offsets[0])); // an empty blob stages nothing
+    sg.in(d.joint_position, B * 96); sg.in(d.joint_velocity, B * 96); sg.in(d.joint_velocity_oldest, B * 96);
+    sg.in(d.base_position, B * 24); sg.in(d.base_orientation, B * 32); sg.in(d.base_linear_velocity, B * 24);
+    sg.in(d.base_angular_velocity, B * 24); sg.in(d.contact, B * 4);
+    sg.inout(d.limb_state, B * 4); sg.inout(d.store_flag, B * 4); sg.inout(d.stored_joint_position, B * 96);
+    sg.inout(d.leg_mode, B * 4); sg.inout(d.pid_error_last, B * 96); sg.inout(d.pid_error_integral, B * 96);
+    sg.inout(d.support, B * 4);
     // the efforts travel both ways: robots that are skipped, or whose solve fails under QLAMD_ON_FAILURE_KEEP, keep theirs
-    const int i_out[4] = {sg.add(io->joint_effort, B * 96, true, true), sg.add(io->leg_state_code, B * 4, false, true),
-                          sg.add(io->status, B * 4, false, true), sg.add(io->message_status, B * 4, false, true)};
-    const int i_cmd = sg.add(io->command, cmd_bytes, true, true);
-    const int i_ws = sg.add(io->working_set, B * 4, true, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    d.offsets = sg.dev<const int64_t>(i_off);
-    d.messages = (const uint8_t *)(sg.base + sg.items[i_msg].off) - io->offsets[0];
-    d.joint_position = sg.dev<const double>(i_in[0]); d.joint_velocity = sg.dev<const double>(i_in[1]);
-    d.joint_velocity_oldest = sg.dev<const double>(i_in[2]); d.base_position = sg.dev<const double>(i_in[3]);
-    d.base_orientation = sg.dev<const double>(i_in[4]); d.base_linear_velocity = sg.dev<const double>(i_in[5]);
-    d.base_angular_velocity = sg.dev<const double>(i_in[6]); d.contact = sg.dev<const uint8_t>(i_in[7]);
-    d.limb_state = sg.dev<int8_t>(i_io[0]); d.store_flag = sg.dev<uint8_t>(i_io[1]);
-    d.stored_joint_position = sg.dev<double>(i_io[2]); d.leg_mode = sg.dev<uint8_t>(i_io[3]);
-    d.pid_error_last = sg.dev<double>(i_io[4]); d.pid_error_integral = sg.dev<double>(i_io[5]);
-    d.support = sg.dev<uint8_t>(i_io[6]);
-    d.joint_effort = sg.dev<double>(i_out[0]); d.leg_state_code = sg.dev<int8_t>(i_out[1]);
-    d.status = sg.dev<int32_t>(i_out[2]); d.message_status = sg.dev<int32_t>(i_out[3]);
-    d.command = sg.dev<char>(i_cmd);
-    d.working_set = sg.dev<uint32_t>(i_ws);
+    sg.inout(d.joint_effort, B * 96);
+    sg.out(d.leg_state_code, B * 4); sg.out(d.status, B * 4); sg.out(d.message_status, B * 4);
+    sg.inout(d.command, cmd_bytes); sg.inout(d.working_set, B * 4);
   }
+  if (const int rc = sg.upload(ctx, st)) return rc;
   // context scratch: the leg state codes when the caller does not want them, and the command block when the caller
   // keeps none (then no command outlives the call: the flags are cleared first)
   const size_t scratch = align256(B * 4) + (d.command ? 0 : cmd_bytes);
@@ -1187,9 +1121,12 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
   //    commands, nudged foot targets -- the state machine of qlamd_leg_state_machine_batch with the mode merge in front,
   //    run by the parser's blocks on the command they have just put in force; robots without a command get their status
   //    here and are left alone by every kernel of the tick
-  const LegStatePtrs ls{U(kCmdSup), nullptr, d.contact, D(kCmdPhase), d.joint_position, d.limb_state, d.store_flag,
-                        d.stored_joint_position, D(kCmdJoint), D(kCmdFootP), d.support,
-                        d.leg_state_code ? d.leg_state_code : (int8_t *)ctx->tick_ws, U(kCmdMode), d.leg_mode, live, d.status};
+  LegStatePtrs ls{}; // (is_footstep: derived from the modes)
+  ls.support_leg = U(kCmdSup); ls.contact = d.contact; ls.phase = D(kCmdPhase); ls.joint_position = d.joint_position;
+  ls.limb_state = d.limb_state; ls.store_flag = d.store_flag; ls.stored_joint_position = d.stored_joint_position;
+  ls.joint_command = D(kCmdJoint); ls.foot_target = D(kCmdFootP); ls.support = d.support;
+  ls.code = d.leg_state_code ? d.leg_state_code : (int8_t *)ctx->tick_ws;
+  ls.msg_mode = U(kCmdMode); ls.leg_mode = d.leg_mode; ls.live = live; ls.status = d.status;
   // (large batches: its own launch, one robot per lane, 256 per block -- the parser is bandwidth-bound there and four
   // busy lanes at the tail of every block cost more than a launch: 402 against 365 us at 65 536 robots)
   const bool one_launch = batch <= 16384;
@@ -1208,22 +1145,19 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
     // and pay for the balance kernel's registers and LDS instead (65 536 robots: 381 us fused, 365 us apart)
     if (!(sp.period > 0.0) || !(sp.accel_window > 0.0)) return QLAMD_ERR_INVALID_ARGUMENT;
     TickSwingArgs ta;
-    for (int k = 0; k < 3; k++) { ta.SP.kp[k] = sp.kp[k]; ta.SP.kd[k] = sp.kd[k]; }
-    ta.SP.period = sp.period; ta.SP.accel_window = sp.accel_window; ta.SP.accel_scale = sp.accel_scale;
-    ta.SP.gravity = sp.gravity;
-    memcpy(ta.pid.p, pid->p, sizeof(ta.pid.p)); memcpy(ta.pid.i, pid->i, sizeof(ta.pid.i)); memcpy(ta.pid.d, pid->d, sizeof(ta.pid.d));
-    memcpy(ta.pid.i_max, pid->i_max, sizeof(ta.pid.i_max)); memcpy(ta.pid.i_min, pid->i_min, sizeof(ta.pid.i_min));
-    memcpy(ta.pid.lower, pid->lower, sizeof(ta.pid.lower)); memcpy(ta.pid.upper, pid->upper, sizeof(ta.pid.upper));
-    ta.pid.antiwindup = pid->antiwindup;
+    ta.SP = swing_params_dev(sp);
+    ta.pid = pid_params_dev(*pid);
     ta.s = SwingPtrs{d.joint_position, d.joint_velocity, d.joint_velocity_oldest, D(kCmdFootP), D(kCmdFootV), nullptr, d.support};
     ta.b = SwingBranchPtrs{d.base_orientation, D(kCmdJoint), d.leg_mode, d.pid_error_last, d.pid_error_integral, live};
     ta.period = period;
     // (working_set: the robot's final working set of its previous tick in, this tick's out -- in place: a robot's set is read
     // and written by its own 16 lanes only)
-    const coop::CoopPtrs cp{d.joint_position, d.base_position, d.base_orientation, d.base_linear_velocity,
-                            d.base_angular_velocity, D(kCmdPos), D(kCmdQuat), D(kCmdLin), D(kCmdAng), d.support,
-                            nullptr, nullptr, live, 1, nullptr, d.working_set, d.working_set,
-                            (uint32_t *)ctx->place_sync + kSyncWarmRetries};
+    coop::CoopPtrs cp{};
+    cp.q = d.joint_position; cp.pos = d.base_position; cp.quat = d.base_orientation; cp.linvel = d.base_linear_velocity;
+    cp.angvel = d.base_angular_velocity; cp.dpos = D(kCmdPos); cp.dquat = D(kCmdQuat); cp.dlinvel = D(kCmdLin);
+    cp.dangvel = D(kCmdAng); cp.stance = d.support; cp.live = live; cp.support_only = 1;
+    cp.prev_working_set = cp.working_set = d.working_set;
+    cp.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
     const unsigned nbal = (unsigned)((batch + 3) / 4), nsw = (unsigned)((4 * batch + 63) / 64);
     if (d.working_set)
       hipLaunchKernelGGL(tick_solve_kernel<true>, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort,
@@ -1262,8 +1196,7 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
     rc = swing_branch_impl(ctx, &sp, pid, &sw, &ex, live, period, batch, d.joint_effort, QLAMD_MEM_DEVICE, stream);
     if (rc != QLAMD_OK) return rc;
   }
-  if (memory == QLAMD_MEM_HOST) return sg.finish(st);
-  return QLAMD_OK;
+  return sg.finish(st);
 }
 
 } // extern "C"

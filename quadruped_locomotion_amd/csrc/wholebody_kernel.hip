@@ -480,6 +480,11 @@ __global__ __launch_bounds__(64, 2) void wholebody_solve_kernel(const DevicePara
   }
 }
 
+using WbSolveLayout = KernargLayout<decltype(&wholebody_solve_kernel<false, true>)>;
+QL_KERNARG_MIRROR(WbSolveLayout, WbSolveArgs, true, Pp, W, s, B, tau, grf, status, pp);
+static_assert(std::is_same<decltype(&wholebody_solve_kernel<false, true>), decltype(&wholebody_solve_kernel<true, true>)>::value,
+              "every instantiation of wholebody_solve_kernel takes the same parameters");
+
 } // namespace
 
 extern "C" {
@@ -513,25 +518,14 @@ int qlamd_wholebody_dynamics_batch(qlamd_context *ctx, const qlamd_wholebody_bat
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  WbPtrs s{in->joint_position, in->joint_velocity, in->base_orientation, in->base_linear_velocity,
-           in->base_angular_velocity, nullptr, nullptr, nullptr, nullptr};
+  WbPtrs s{}; // (the dynamics read the state only)
+  s.q = in->joint_position; s.qd = in->joint_velocity; s.quat = in->base_orientation;
+  s.linvel = in->base_linear_velocity; s.angvel = in->base_angular_velocity;
   double *dM = mass_matrix, *dh = nonlinear_effects, *dJ = contact_jacobian;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    sg.add(in->joint_position, B * 96, true, false);
-    sg.add(in->joint_velocity, B * 96, true, false);
-    sg.add(in->base_orientation, B * 32, true, false);
-    sg.add(in->base_linear_velocity, B * 24, true, false);
-    sg.add(in->base_angular_velocity, B * 24, true, false);
-    sg.add(mass_matrix, B * 324 * 8, false, true);
-    sg.add(nonlinear_effects, B * 18 * 8, false, true);
-    sg.add(contact_jacobian, B * 216 * 8, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s.q = sg.dev<const double>(0); s.qd = sg.dev<const double>(1); s.quat = sg.dev<const double>(2);
-    s.linvel = sg.dev<const double>(3); s.angvel = sg.dev<const double>(4);
-    dM = sg.dev<double>(5); dh = sg.dev<double>(6); dJ = sg.dev<double>(7);
-  }
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.q, B * 96); sg.in(s.qd, B * 96); sg.in(s.quat, B * 32); sg.in(s.linvel, B * 24); sg.in(s.angvel, B * 24);
+  sg.out(dM, B * 324 * 8); sg.out(dh, B * 18 * 8); sg.out(dJ, B * 216 * 8);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const coop::WbParamsDev W = wb_params_of(ctx, 0.0, 0.0, gravity);
   // Two layouts of the same arithmetic.  Measured (profiles/r2): the row form 9.8 / 13.9 / 22.5 us at 4096 / 8192 / 16 384
   // robots against 13.1 / 14.3 / 19.8 for the leg form, which then pulls away (1 M robots: 0.92 ms against 1.22 ms).
@@ -562,8 +556,7 @@ int qlamd_wholebody_dynamics_batch(qlamd_context *ctx, const qlamd_wholebody_bat
     }
   }
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
-  if (memory == QLAMD_MEM_HOST) return sg.finish(st);
-  return QLAMD_OK;
+  return sg.finish(st);
 }
 
 int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params *params,
@@ -587,49 +580,30 @@ int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params
   WbPtrs s{in->joint_position, in->joint_velocity, in->base_orientation, in->base_linear_velocity,
            in->base_angular_velocity, in->desired_base_acceleration, in->desired_joint_acceleration, in->support_leg,
            in->surface_normal};
-  double *dtau = joint_effort, *dgrf = contact_force;
-  int32_t *dst = status;
-  Staged sg;
-  if (memory == QLAMD_MEM_HOST) {
-    sg.add(in->joint_position, B * 96, true, false);
-    sg.add(in->joint_velocity, B * 96, true, false);
-    sg.add(in->base_orientation, B * 32, true, false);
-    sg.add(in->base_linear_velocity, B * 24, true, false);
-    sg.add(in->base_angular_velocity, B * 24, true, false);
-    sg.add(in->desired_base_acceleration, B * 48, true, false);
-    sg.add(in->desired_joint_acceleration, B * 96, true, false);
-    sg.add(in->support_leg, B * 4, true, false);
-    sg.add(in->surface_normal, B * 96, true, false);
-    const bool keep = ctx->params.keep_on_failure != 0; // entries the kernel leaves alone come back as they went up
-    sg.add(joint_effort, B * 96, keep, true);
-    sg.add(contact_force, B * 96, keep, true);
-    sg.add(status, B * 4, false, true);
-    const int rc = sg.upload(ctx, st);
-    if (rc != QLAMD_OK) return rc;
-    s = WbPtrs{sg.dev<const double>(0), sg.dev<const double>(1), sg.dev<const double>(2), sg.dev<const double>(3),
-               sg.dev<const double>(4), sg.dev<const double>(5), sg.dev<const double>(6), sg.dev<const uint8_t>(7),
-               sg.dev<const double>(8)};
-    dtau = sg.dev<double>(9); dgrf = sg.dev<double>(10); dst = sg.dev<int32_t>(11);
-  }
+  const bool keep = ctx->params.keep_on_failure != 0; // entries the kernel leaves alone come back as they went up
+  Staged sg(memory == QLAMD_MEM_HOST);
+  sg.in(s.q, B * 96); sg.in(s.qd, B * 96); sg.in(s.quat, B * 32); sg.in(s.linvel, B * 24); sg.in(s.angvel, B * 24);
+  sg.in(s.a_des, B * 48); sg.in(s.qdd, B * 96); sg.in(s.stance, B * 4); sg.in(s.normals, B * 96);
+  sg.out(joint_effort, B * 96, keep); sg.out(contact_force, B * 96, keep); sg.out(status, B * 4);
+  if (const int rc = sg.upload(ctx, st)) return rc;
   const coop::WbParamsDev W = wb_params_of(ctx, params->torque_weight, params->torque_limit, params->gravity);
   const unsigned grid = (unsigned)((batch + 3) / 4);
   const bool warm = pp.prev_working_set || pp.working_set;
 #define QL_LAUNCH_WB(PERLEG)                                                                                                   \
   do {                                                                                                                         \
     if (warm)                                                                                                                  \
-      hipLaunchKernelGGL((wholebody_solve_kernel<PERLEG, true>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch, dtau, \
-                         dgrf, dst, pp);                                                                                       \
+      hipLaunchKernelGGL((wholebody_solve_kernel<PERLEG, true>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,      \
+                         joint_effort, contact_force, status, pp);                                                             \
     else                                                                                                                       \
       hipLaunchKernelGGL((wholebody_solve_kernel<PERLEG, false>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,     \
-                         dtau, dgrf, dst, pp);                                                                                 \
+                         joint_effort, contact_force, status, pp);                                                             \
   } while (0)
   if (s.normals) QL_LAUNCH_WB(true);
   else QL_LAUNCH_WB(false);
 #undef QL_LAUNCH_WB
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   { const int rc = finish_placement(ctx, pl, batch, st); if (rc != QLAMD_OK) return rc; }
-  if (memory == QLAMD_MEM_HOST) return sg.finish(st);
-  return QLAMD_OK;
+  return sg.finish(st);
 }
 
 } // extern "C"
