@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 #define QLAMD_VERSION_MAJOR 0
-#define QLAMD_VERSION_MINOR 7
+#define QLAMD_VERSION_MINOR 8
 
 /* ---- return codes of the API calls ------------------------------------- */
 #define QLAMD_OK 0
@@ -393,8 +393,9 @@ typedef struct qlamd_placement {
    * placement (QLAMD_PLACEMENT_AUTO counts the table as a warm start), QLAMD_STATE_RECORDS and per-leg normals work with it as
    * with prev_working_set, and so do the checks: a word that is no working set is ignored, an answer that fails the final
    * check is never returned.  Host-memory calls and qlamd_set_robots_per_wave(16 | 64) refuse it as they refuse any warm start.
-   * Not taken by qlamd_place_next_call (QLAMD_ERR_INVALID_ARGUMENT): the whole-body step keeps two words per robot, and
-   * qlamd_full_tick_batch its one-word working_set.  16 bytes read and 4 written per robot and step.
+   * Not taken by qlamd_place_next_call (QLAMD_ERR_INVALID_ARGUMENT): the whole-body step takes a table of its own, of 64-bit
+   * words, through qlamd_wholebody_solve_placed_batch, and the whole tick through qlamd_tick_batch::set_memory.  16 bytes read
+   * and 4 written per robot and step.
    * Last member: an initialiser written for the structure without it leaves it NULL. */
   uint32_t *set_memory;
 } qlamd_placement;
@@ -417,8 +418,8 @@ int qlamd_force_distribution_placed_batch(qlamd_context *ctx, const double *join
  * robot_order / iterations index the call's problems; with prev_iterations / next_robot_order the placement for the
  * caller's next call is made by qlamd_placement_from_iterations' launches behind the solve, on its stream.
  * placement = NULL withdraws a pending one.  (qlamd_balance_solve_batch and the other entries ignore it.)
- * A placement with set_memory is refused (QLAMD_ERR_INVALID_ARGUMENT, nothing pending afterwards): the table is the balance
- * step's.
+ * A placement with set_memory is refused (QLAMD_ERR_INVALID_ARGUMENT, nothing pending afterwards): that table is the balance
+ * step's (the whole-body step's comes through qlamd_wholebody_solve_placed_batch).
  * Warm start: qlamd_wholebody_solve_batch also takes prev_working_set / working_set this way, with TWO words per robot
  * ([B][2] uint32 = 64 bits, low word first: bit 11 leg + kind, kinds 0..4 as for the balance step, 5 + 2k / 6 + 2k the upper /
  * lower torque bound of the leg's joint k; bits 44..47: the support legs the set was reached with); the two dense entries start
@@ -772,6 +773,27 @@ int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params
                                 const qlamd_wholebody_batch *in, int64_t batch, double *joint_effort,
                                 double *contact_force, int32_t *status, int memory, void *stream);
 
+/* The same step with its placement as an argument, and with A WORKING SET PER SUPPORT SET (qlamd_placement::set_memory has the
+ * reasons).  QLAMD_MEM_DEVICE only (anything else: QLAMD_ERR_INVALID_ARGUMENT).
+ *   placement   or NULL: what qlamd_place_next_call carries for this step -- robot_order, iterations, prev_iterations /
+ *               next_robot_order, policy and the 64-bit prev_working_set / working_set ([B][2] uint32).  placement->set_memory,
+ *               the balance step's 32-bit table, must be NULL.
+ *   set_memory  [B][4] 64-bit words or NULL, 32-byte aligned, zero-filled before the first step, in/out: takes the place of
+ *               placement->prev_working_set (giving both is QLAMD_ERR_INVALID_ARGUMENT).  A word is the step's 64-bit set: rows
+ *               in bits 0..43, the support legs it was reached with in bits 44..47, 0 = no record (low uint32 first, as in
+ *               [B][2]).  The slot of a support mask is QLAMD_SET_MEMORY_SLOT(mask).  A robot starts from the word in the slot of
+ *               its support legs if the legs recorded there are its support legs now, and otherwise builds a set by rounds;
+ *               with QLAMD_STATUS_OK it writes its final set with its legs to that slot; with any other status, and when the
+ *               second attempt of a rejected start ran, it writes 0 there.  The three other slots are neither read for
+ *               arithmetic nor written.  placement->working_set may be given beside it as a plain output.
+ *               QLAMD_PLACEMENT_AUTO counts the table as a warm start.  Per-leg normals work with it.
+ * With set_memory == NULL the call is qlamd_place_next_call(ctx, placement) followed by qlamd_wholebody_solve_batch, bit for
+ * bit.  A placement pending on the context (qlamd_place_next_call) is neither taken nor cleared.  Any refusal writes nothing. */
+int qlamd_wholebody_solve_placed_batch(qlamd_context *ctx, const qlamd_wholebody_params *params,
+                                       const qlamd_wholebody_batch *in, int64_t batch, const qlamd_placement *placement,
+                                       uint64_t *set_memory, double *joint_effort, double *contact_force, int32_t *status,
+                                       int memory, void *stream);
+
 /* ---- the whole control tick in one call (SURVEY.md section 8 row a1 with rows f1 and f2) -----------------------
  * What the plugin does between one /desired_robot_state message and 12 effort commands:
  *   baseCommandCallback (ros_balance_controller.cpp:761-1083)   message -> desired base state, leg modes, targets
@@ -829,6 +851,26 @@ typedef struct qlamd_tick_batch {
                                            The context remembers which tick of the loop comes next for the array it saw last: a
                                            context that alternates between batches starts the loop over each time (slower, never
                                            wrong).  Efforts are those of the unplaced tick bit for bit (cold) */
+  uint32_t *set_memory;                 /* [B][4] or NULL: A WORKING SET PER SUPPORT SET for the tick's balance solve, in the place
+                                           of working_set (giving both: QLAMD_ERR_INVALID_ARGUMENT, nothing is written); in/out,
+                                           zero-filled before the first tick.  Word format, slot rule (QLAMD_SET_MEMORY_SLOT) and
+                                           the read / write rules are those of qlamd_placement::set_memory, for the support legs of
+                                           THIS tick (what the tick's state machine has just written to `support`): that slot is
+                                           read; the final set with its legs is written back with QLAMD_STATUS_OK, 0 with any other
+                                           solve status and when the second attempt of a rejected start ran; the three other slots
+                                           are neither read for arithmetic nor written; a robot skipped with
+                                           QLAMD_STATUS_NO_COMMAND keeps all four words.  QLAMD_MEM_DEVICE: 16-byte aligned, else
+                                           QLAMD_ERR_INVALID_ARGUMENT; QLAMD_MEM_HOST: any alignment (staged, 16 bytes per robot
+                                           each way).  Works with and without placement_state.  The one-lane kernels of
+                                           qlamd_set_robots_per_wave(16 | 64) know no warm start: they IGNORE the table as they
+                                           ignore working_set (its words stay as they are) */
+  int32_t *iterations;                  /* [B] or NULL, out: qlamd_placement::iterations of the tick's balance solve, in every
+                                           lane-cooperative form of the tick (cold, working_set, set_memory, one launch or
+                                           several; with placement_state a copy of the tick's own counts).  Robots skipped with
+                                           QLAMD_STATUS_NO_COMMAND are left untouched; so is the whole array with
+                                           qlamd_set_robots_per_wave(16 | 64), whose kernels do not count.
+                                           (set_memory and iterations are the last members: an initialiser written for the
+                                           structure without them leaves them NULL.) */
 } qlamd_tick_batch;
 
 size_t qlamd_tick_command_bytes(int64_t batch);

@@ -31,6 +31,7 @@ EXPORTS = (
     "qlamd_full_tick_batch", "qlamd_set_option", "qlamd_tick_command_bytes", "qlamd_weighted_lsq_qp_batch",
     "qlamd_reserve", "qlamd_balance_solve_placed_batch", "qlamd_force_distribution_placed_batch",
     "qlamd_placement_from_iterations", "qlamd_place_next_call", "qlamd_get_counter", "qlamd_set_memory_slot",
+    "qlamd_wholebody_solve_placed_batch",
 )
 
 
@@ -97,7 +98,7 @@ TICK_FIELDS = (("messages", np.uint8), ("offsets", np.int64), ("joint_position",
                ("limb_state", np.int8), ("store_flag", np.uint8), ("stored_joint_position", np.float64), ("leg_mode", np.uint8), ("support", np.uint8),
                ("pid_error_last", np.float64), ("pid_error_integral", np.float64), ("joint_effort", np.float64),
                ("leg_state_code", np.int8), ("status", np.int32), ("message_status", np.int32), ("command", np.uint8),
-               ("working_set", np.uint32), ("placement_state", np.int32))
+               ("working_set", np.uint32), ("placement_state", np.int32), ("set_memory", np.uint32), ("iterations", np.int32))
 
 
 class TickBatch(C.Structure):
@@ -938,6 +939,34 @@ def wholebody_solve_device(ctx, dstate, tau, grf, status, params=None, stream=No
         raise QlamdError(rc, "qlamd_wholebody_solve_batch")
 
 
+def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, stream=None, order=None, iterations=None,
+                                  prev_iterations=None, next_order=None, policy=0, prev_working_set=None, working_set=None,
+                                  set_memory=None):
+    """qlamd_wholebody_solve_placed_batch on torch CUDA tensors; asynchronous.  order / iterations / prev_iterations / next_order:
+    int32 [B]; prev_working_set / working_set: the 64-bit sets as int32 [B, 2] or int64 [B]; set_memory: the working set per support
+    set, int64 [B, 4] (32-byte aligned: the library refuses another), updated in place, instead of prev_working_set."""
+    prm = params if params is not None else default_wholebody_params()
+    wb = _wholebody_batch(dstate, [])
+    B = dstate["q"].shape[0]
+    if set_memory is not None and (str(set_memory.dtype) != "torch.int64" or set_memory.numel() != 4 * B or not set_memory.is_contiguous()):
+        raise ValueError("set_memory must be a contiguous int64 tensor of %d x 4 elements (the 64 bits of a uint64)" % B)
+    for name, t in (("prev_working_set", prev_working_set), ("working_set", working_set)):
+        if t is not None and (t.numel() * t.element_size() != 8 * B or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous tensor of 8 bytes per robot" % name)
+    pl = None
+    if any(t is not None for t in (order, iterations, prev_iterations, next_order, prev_working_set, working_set)):
+        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
+                       _ptr(prev_working_set), _ptr(working_set), None)
+    fn = lib().qlamd_wholebody_solve_placed_batch
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_int, C.c_void_p]
+    rc = fn(ctx._h, C.addressof(prm), C.addressof(wb), B, C.addressof(pl) if pl is not None else None, _ptr(set_memory),
+            tau.data_ptr(), grf.data_ptr() if grf is not None else None, status.data_ptr(), MEM_DEVICE,
+            C.c_void_p(stream) if stream else None)
+    if rc != OK:
+        raise QlamdError(rc, "qlamd_wholebody_solve_placed_batch")
+
+
 def wholebody_dynamics_device(ctx, dstate, M, h, Jc, gravity=9.81, stream=None):
     wb = _wholebody_batch(dstate, [])
     rc = lib().qlamd_wholebody_dynamics_batch(ctx._h, C.byref(wb), C.c_double(gravity), dstate["q"].shape[0],
@@ -972,7 +1001,8 @@ def tick_command_bytes(batch):
 def full_tick(ctx, io, period, index_quirk=1, params=None, pid=None, memory=MEM_HOST, stream=None):
     """qlamd_full_tick_batch.  `io`: dict with the fields of qlamd_tick_batch (TICK_FIELDS: C-contiguous numpy arrays of
     those dtypes for host memory, torch CUDA tensors for device memory; `leg_state_code` and `command` may be None);
-    in/out and out arrays are updated in place."""
+    in/out and out arrays are updated in place.  `set_memory` ([B, 4], in the place of `working_set`) and `iterations` ([B]) are
+    the optional last members; a torch tensor holds their 32-bit words as int32."""
     prm = params if params is not None else default_swing_params()
     pidp = pid if pid is not None else default_joint_pid_params()
     tb = TickBatch()
@@ -984,6 +1014,13 @@ def full_tick(ctx, io, period, index_quirk=1, params=None, pid=None, memory=MEM_
             assert a.dtype == dt and a.flags["C_CONTIGUOUS"], name
         setattr(tb, name, _ptr(a))
     B = int(io["offsets"].shape[0]) - 1
+    sm = io.get("set_memory")
+    if sm is not None:
+        words = sm.numel() if hasattr(sm, "numel") else sm.size
+        if words != 4 * B or (sm.element_size() if hasattr(sm, "element_size") else sm.itemsize) != 4:
+            raise ValueError("set_memory must hold %d x 4 words of 32 bits" % B)
+        if hasattr(sm, "is_contiguous") and not sm.is_contiguous():
+            raise ValueError("set_memory must be contiguous")
     rc = lib().qlamd_full_tick_batch(ctx._h, C.byref(prm), C.byref(pidp), C.byref(tb), float(period), int(index_quirk), B, memory,
                                      C.c_void_p(stream) if stream else None)
     if rc != OK:

@@ -261,6 +261,26 @@ __device__ __forceinline__ int64_t placed_index(const PlacePtrs &pp, int64_t slo
   return i;
 }
 #endif
+// The placement `pl` (checked by placement_ok) for a QLAMD_MEM_DEVICE call of `batch` problems: fills pp / *next as take_placement
+// does.  table: the call warm-starts from a table of its own (the whole-body step's set_memory), which counts as a warm start.
+inline int use_placement(const qlamd_placement &pl, int memory, int64_t batch, bool table, PlacePtrs *pp,
+                         qlamd_placement *next) {
+  if (memory != QLAMD_MEM_DEVICE || batch > INT32_MAX) return QLAMD_ERR_INVALID_ARGUMENT;
+  pp->order = pl.robot_order;
+  pp->iterations = pl.iterations;
+  pp->prev_working_set = reinterpret_cast<const unsigned long long *>(pl.prev_working_set);
+  pp->working_set = reinterpret_cast<unsigned long long *>(pl.working_set);
+  *next = pl;
+  // with a warm start (the whole-body step) and no placement the solving launch writes the identity itself and nothing is
+  // launched behind it (the placement's two launches were 5 of the 23 us of a warm-started whole-body step of 4096 robots)
+  const bool warm = pl.prev_working_set || pl.working_set || table;
+  if (pl.next_robot_order && warm) next->policy = effective_policy(pl.policy, batch, true);
+  if (pl.next_robot_order && next->policy == QLAMD_PLACEMENT_NONE && warm) {
+    pp->identity_out = pl.next_robot_order;
+    next->next_robot_order = nullptr;
+  }
+  return QLAMD_OK;
+}
 // Takes the pending placement of qlamd_place_next_call, if any, for a QLAMD_MEM_DEVICE call of `batch` problems.
 // Returns QLAMD_OK and fills pp / *next (next->next_robot_order != NULL when a following placement was asked for), or
 // QLAMD_ERR_INVALID_ARGUMENT for a host-memory call (the placement's arrays are device arrays).
@@ -271,21 +291,7 @@ inline int take_placement(qlamd_context *ctx, int memory, int64_t batch, PlacePt
   if (!ctx->has_next_placement) return QLAMD_OK;
   const qlamd_placement pl = ctx->next_placement;
   ctx->has_next_placement = false;
-  if (memory != QLAMD_MEM_DEVICE || batch > INT32_MAX) return QLAMD_ERR_INVALID_ARGUMENT;
-  pp->order = pl.robot_order;
-  pp->iterations = pl.iterations;
-  pp->prev_working_set = reinterpret_cast<const unsigned long long *>(pl.prev_working_set);
-  pp->working_set = reinterpret_cast<unsigned long long *>(pl.working_set);
-  *next = pl;
-  // with a warm start (the whole-body step) and no placement the solving launch writes the identity itself and nothing is
-  // launched behind it (the placement's two launches were 5 of the 23 us of a warm-started whole-body step of 4096 robots)
-  const bool warm = pl.prev_working_set || pl.working_set;
-  if (pl.next_robot_order && warm) next->policy = effective_policy(pl.policy, batch, true);
-  if (pl.next_robot_order && next->policy == QLAMD_PLACEMENT_NONE && warm) {
-    pp->identity_out = pl.next_robot_order;
-    next->next_robot_order = nullptr;
-  }
-  return QLAMD_OK;
+  return use_placement(pl, memory, batch, false, pp, next);
 }
 inline int finish_placement(qlamd_context *ctx, const qlamd_placement &pl, int64_t batch, hipStream_t st) {
   if (!pl.next_robot_order) return QLAMD_OK;
@@ -324,7 +330,7 @@ constexpr size_t kSmallHostCall = 256 * 1024; // below this a host-buffer call g
 // and returns QLAMD_OK: the variables keep the caller's pointers.
 class Staged {
  public:
-  static constexpr int kMaxItems = 24; // upload() refuses a call that binds more
+  static constexpr int kMaxItems = 32; // upload() refuses a call that binds more (the whole tick binds 25)
   explicit Staged(bool host_call) : on(host_call) {}
   template <class T> void in(const T *&p, size_t bytes) { bind(p, 0, bytes, true, false); }
   template <class T> void out(T *&p, size_t bytes, bool also_in = false) { bind(p, 0, bytes, also_in, true); }

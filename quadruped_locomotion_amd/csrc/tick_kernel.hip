@@ -173,6 +173,53 @@ __global__ __launch_bounds__(64, 2) void tick_solve_kernel(const DeviceParams *_
 using TickSolveLayout = KernargLayout<decltype(&tick_solve_kernel<true>)>;
 QL_KERNARG_MIRROR(TickSolveLayout, TickSolveArgs, false, Pp, cp, B, effort, status); // (a prefix: the swing blocks' arguments follow)
 
+// The same launch with the balance blocks warm-started from the table (qlamd_tick_batch::set_memory, cp.set_memory): a kernel of
+// its own, so that a tick without the table runs what it ran before the table existed, and a second attempt of its own
+// (balance_kernel.hip, balance_table_retry, has the reason).  The first attempt has left 0 in the slot of a rejected robot.
+__device__ __attribute__((noinline, noreturn)) void tick_table_retry(const TickSolveArgs *args, double *tab, double *rows, double *nrm, bool rejected) {
+  const TickSolveArgs &a = *args;
+  const int row = threadIdx.x >> 4;
+  int64_t ir = (int64_t)blockIdx.x * 4 + row;
+  if (ir >= a.B) ir = a.B - 1;
+  coop::CoopPtrs cold = a.cp;
+  cold.prev_working_set = nullptr; cold.working_set = nullptr; cold.warm_retries = nullptr; cold.set_memory = nullptr;
+  (void)coop::coop_robot<false, 64, false>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.effort, nullptr, a.status);
+  __builtin_amdgcn_endpgm();
+}
+__global__ __launch_bounds__(64, 2) void tick_table_kernel(const DeviceParams *__restrict__ Pp, const coop::CoopPtrs cp, int64_t B,
+                                                           double *__restrict__ effort, int32_t *__restrict__ status,
+                                                           unsigned nbal, const TickSwingArgs sw) {
+  __shared__ double tab[4 * kTabPerLeg];
+  __shared__ double rows[4 * coop::kCoopLdsDoubles];
+  __shared__ double nrm[coop::kCoopNrmDoubles];
+  QL_BLOCK_STAMP(2);
+  if (blockIdx.x < nbal) {
+    const int row = threadIdx.x >> 4;
+    int64_t i = (int64_t)blockIdx.x * 4 + row;
+    const bool live = i < B;
+    if (!live) i = B - 1;
+    const bool rejected = coop::coop_robot<false, 64, true, false, false, true, true>(*Pp, cp, i, live, tab, rows + row * coop::kCoopLdsDoubles, nrm, effort,
+                                                                                     nullptr, status);
+    if (__builtin_expect(Pp->warm_fallback && __builtin_amdgcn_ballot_w64(rejected) != 0ull, 0)) {
+      __syncthreads();
+      tick_table_retry(coop::kernel_arguments_again<TickSolveArgs>(), tab, rows, nrm, rejected);
+    }
+  } else {
+    swing_branch_block(*Pp, sw.SP, sw.pid, sw.s, sw.b, sw.period, B, effort, (int64_t)(blockIdx.x - nbal), tab);
+  }
+  QL_BLOCK_STAMP(3);
+}
+using TickTableLayout = KernargLayout<decltype(&tick_table_kernel)>;
+QL_KERNARG_MIRROR(TickTableLayout, TickSolveArgs, false, Pp, cp, B, effort, status);
+
+// qlamd_tick_batch::iterations beside placement_state: the counts of this tick (the tick's own array, which the placed loop goes
+// on using) to the caller's array, the robots without a command left out
+__global__ __launch_bounds__(256) void tick_iterations_copy_kernel(const int32_t *__restrict__ src, const uint8_t *__restrict__ live,
+                                                                   int32_t *__restrict__ dst, int64_t B) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < B && live[i]) dst[i] = src[i];
+}
+
 // ---- leg state machine (row f2): one robot per lane, flags and a few doubles in, flags out ----------
 struct LegStatePtrs {
   const uint8_t *support_leg, *is_footstep, *contact;
@@ -1070,6 +1117,9 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
       !io->pid_error_last || !io->pid_error_integral || !io->joint_effort || !io->status || !io->message_status)
     return QLAMD_ERR_INVALID_ARGUMENT;
   if (memory != QLAMD_MEM_DEVICE && memory != QLAMD_MEM_HOST) return QLAMD_ERR_INVALID_ARGUMENT;
+  // the table takes the place of working_set; on the device a robot's four words are one 16-byte load (a host table is staged)
+  if (io->set_memory && (io->working_set || (memory == QLAMD_MEM_DEVICE && (reinterpret_cast<uintptr_t>(io->set_memory) & 15u))))
+    return QLAMD_ERR_INVALID_ARGUMENT;
   if (batch == 0) return QLAMD_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
   hipStream_t st = (hipStream_t)stream;
@@ -1093,7 +1143,8 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
     // the efforts travel both ways: robots that are skipped, or whose solve fails under QLAMD_ON_FAILURE_KEEP, keep theirs
     sg.inout(d.joint_effort, B * 96);
     sg.out(d.leg_state_code, B * 4); sg.out(d.status, B * 4); sg.out(d.message_status, B * 4);
-    sg.inout(d.command, cmd_bytes); sg.inout(d.working_set, B * 4);
+    sg.inout(d.command, cmd_bytes); sg.inout(d.working_set, B * 4); sg.inout(d.set_memory, B * 16);
+    sg.inout(d.iterations, B * 4); // (both ways: the robots without a command keep theirs)
   }
   if (const int rc = sg.upload(ctx, st)) return rc;
   // context scratch: the leg state codes when the caller does not want them, and the command block when the caller
@@ -1158,8 +1209,13 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
     cp.dangvel = D(kCmdAng); cp.stance = d.support; cp.live = live; cp.support_only = 1;
     cp.prev_working_set = cp.working_set = d.working_set;
     cp.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
+    cp.iterations = d.iterations;
+    cp.set_memory = d.set_memory;
     const unsigned nbal = (unsigned)((batch + 3) / 4), nsw = (unsigned)((4 * batch + 63) / 64);
-    if (d.working_set)
+    if (d.set_memory)
+      hipLaunchKernelGGL(tick_table_kernel, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort, d.status, nbal,
+                         ta);
+    else if (d.working_set)
       hipLaunchKernelGGL(tick_solve_kernel<true>, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort,
                          d.status, nbal, ta);
     else
@@ -1174,6 +1230,9 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
     memset(&pl, 0, sizeof(pl));
     const bool coop = pick_rpw(ctx, batch) == 4; // (the one-lane kernels of the cross-check know neither warm start nor placement)
     if (coop) pl.prev_working_set = pl.working_set = d.working_set; // warm start, in place (NULL: cold)
+    if (coop) pl.set_memory = d.set_memory;                         // ... or from the table (instead: checked above)
+    if (coop) pl.iterations = d.iterations;
+    bool copy_iterations = false;
     if (io->placement_state && memory == QLAMD_MEM_DEVICE && coop) {
       // the caller's loop of include/qlamd.h on the tick's own state: tick k runs in order[k & 1] (identity on the first tick),
       // writes iters[k & 1] and makes order[(k + 1) & 1] from iters[(k - 1) & 1] (zeros on the first tick: the identity)
@@ -1185,12 +1244,18 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
       const int64_t k = ctx->tick_place_count++;
       pl.robot_order = k == 0 ? nullptr : ps + (k & 1) * B;
       pl.iterations = ps + 2 * B + (k & 1) * B;
+      copy_iterations = d.iterations != nullptr;
       pl.prev_iterations = ps + 2 * B + ((k + 1) & 1) * B;
       pl.next_robot_order = ps + ((k + 1) & 1) * B;
       pl.policy = QLAMD_PLACEMENT_AUTO;
     }
     rc = balance_launch(ctx, sb, QLAMD_STATE_FIELDS, nullptr, live, 1, pl, batch, d.joint_effort, nullptr, d.status, st);
     if (rc != QLAMD_OK) return rc;
+    if (copy_iterations) {
+      hipLaunchKernelGGL(tick_iterations_copy_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, pl.iterations, live,
+                         d.iterations, batch);
+      if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
+    }
     const qlamd_swing_batch sw{d.joint_position, d.joint_velocity, d.joint_velocity_oldest, D(kCmdFootP), D(kCmdFootV), d.support, nullptr};
     const qlamd_swing_branch_extra ex{d.base_orientation, D(kCmdJoint), d.leg_mode, d.pid_error_last, d.pid_error_integral};
     rc = swing_branch_impl(ctx, &sp, pid, &sw, &ex, live, period, batch, d.joint_effort, QLAMD_MEM_DEVICE, stream);

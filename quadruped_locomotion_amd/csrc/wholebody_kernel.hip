@@ -308,12 +308,16 @@ __global__ __launch_bounds__(64) void wholebody_dynamics_leg_kernel(const Device
 // computed in (lane 4 leg + c: body c of the leg = force component c = joint c), force_qp_coop.hpp with its torque rows
 // -- no exchange through LDS, no general dense solver.
 // kWarm: the QP starts from the working set handed in through qlamd_place_next_call (force_qp_coop.hpp; 44 rows: 64 bits).
+// kTable (with kWarm; wholebody_table_kernel): the set a robot starts from is the 64-bit word of its support set in its four of
+// set_memory ([B][4], qlamd_wholebody_solve_placed_batch), and its final set goes back there (balance_coop.hpp, kTable)
 // wholebody_robot: the step of the robot in my row (i; live: the row holds one).  Returns whether its warm start was rejected.
 constexpr int kWbLdsDoubles = 4 * kTabPerLeg + 4 * coop::kCoopLdsDoubles + coop::kForceQpNrmRowsTorque * 64;
-template <bool kPerLeg, bool kWarm>
+template <bool kPerLeg, bool kWarm, bool kTable = false>
 __device__ __forceinline__ bool wholebody_robot(const DeviceParams &P, const coop::WbParamsDev &W, const WbPtrs &s, int64_t i, bool live,
                                                 double *__restrict__ tau_out, double *__restrict__ grf_out,
-                                                int32_t *__restrict__ status_out, const PlacePtrs &pp, double *lds) {
+                                                int32_t *__restrict__ status_out, const PlacePtrs &pp, double *lds,
+                                                unsigned long long *set_memory = nullptr) {
+  static_assert(!kTable || kWarm, "the table is a warm start");
   using namespace coop;
   double *tab = lds, *rows = lds + 4 * kTabPerLeg, *nrm = rows + 4 * kCoopLdsDoubles;
   TabStage ts;
@@ -329,7 +333,13 @@ __device__ __forceinline__ bool wholebody_robot(const DeviceParams &P, const coo
   const uint32_t sm = *reinterpret_cast<const uint32_t *>(s.stance + 4 * i);
   unsigned long long warm_set = 0ull;
   bool build_set = false;
-  if constexpr (kWarm) warm_set = pp.prev_working_set ? pp.prev_working_set[i] : 0ull;
+  // (the table: the robot's four words in two 16-byte loads, issued here with the rest -- which of them counts is known once the
+  // support flags have arrived)
+  ulonglong2 mem01 = {0ull, 0ull}, mem23 = {0ull, 0ull};
+  if constexpr (kTable) {
+    const ulonglong2 *m2 = reinterpret_cast<const ulonglong2 *>(set_memory + 4 * i);
+    mem01 = m2[0]; mem23 = m2[1];
+  } else if constexpr (kWarm) warm_set = pp.prev_working_set ? pp.prev_working_set[i] : 0ull;
   double nWl[3] = {0.0, 0.0, 1.0};
   if (kPerLeg) { nWl[0] = s.normals[12 * i + 3 * leg]; nWl[1] = s.normals[12 * i + 3 * leg + 1]; nWl[2] = s.normals[12 * i + 3 * leg + 2]; }
   ts.commit(tab);
@@ -337,10 +347,13 @@ __device__ __forceinline__ bool wholebody_robot(const DeviceParams &P, const coo
                                        ((sm & 0xFF000000u) ? 8u : 0u))
                                     : 0u;
   const int nS = __popc(stance_legs);
+  const unsigned mem_slot = QLAMD_SET_MEMORY_SLOT(stance_legs);
+  if constexpr (kTable) warm_set = mem_slot == 0u ? mem01.x : mem_slot == 1u ? mem01.y : mem_slot == 2u ? mem23.x : mem23.y;
   if constexpr (kWarm) { // a set remembers the support legs it was reached with (bits 44..47); other legs now: a cold start (balance_coop.hpp)
     const unsigned from = (unsigned)(warm_set >> 44) & 0xFu;
     warm_set = (from != 0u && from != stance_legs) ? 0ull : (warm_set & ((1ull << 44) - 1ull));
-    build_set = pp.prev_working_set != nullptr && from != stance_legs; // (no record, or other legs: the set is built by rounds)
+    if constexpr (kTable) build_set = from != stance_legs; // (the shared slot holds another support set's word, or none yet)
+    else build_set = pp.prev_working_set != nullptr && from != stance_legs; // (no record, or other legs: the set is built by rounds)
   }
   // support legs first (balance_coop.hpp): `leg` is my SLOT in the row, aleg the leg behind it; what was loaded by leg moves
   // to the lane of its slot
@@ -438,7 +451,13 @@ __device__ __forceinline__ bool wholebody_robot(const DeviceParams &P, const coo
   if (lr == 0 && live) {
     status_out[i] = st;
     if (pp.iterations) pp.iterations[i] = st == kStatusNotPd ? 0 : qp_iters;
-    if constexpr (kWarm) { if (pp.working_set) pp.working_set[i] = st == kStatusOk ? (final_set | ((unsigned long long)stance_legs << 44)) : 0ull; }
+    if constexpr (kWarm) {
+      const unsigned long long word = st == kStatusOk ? (final_set | ((unsigned long long)stance_legs << 44)) : 0ull;
+      if (pp.working_set) pp.working_set[i] = word;
+      // (the table: one 8-byte word, the slot of these support legs.  A robot that goes through the second attempt ends with 0
+      // there -- known here already -- so the second attempt needs no table logic of its own: balance_coop.hpp)
+      if constexpr (kTable) set_memory[4 * i + mem_slot] = (P.warm_fallback == 2 && final_set != 0ull) ? 0ull : word;
+    }
   }
   bool rejected = false;
   if constexpr (kWarm) {
@@ -479,6 +498,40 @@ __global__ __launch_bounds__(64, 2) void wholebody_solve_kernel(const DevicePara
     }
   }
 }
+
+// ... warm-started from the table: a kernel of its own, so that a launch without the table runs what it ran before the table
+// existed; its second attempt is a function of its own as well (balance_kernel.hip, balance_table_retry, has the reason)
+struct WbTableArgs { const DeviceParams *Pp; coop::WbParamsDev W; WbPtrs s; int64_t B; double *tau, *grf; int32_t *status; PlacePtrs pp; unsigned long long *set_memory; };
+template <bool kPerLeg>
+__device__ __attribute__((noinline, noreturn)) void wholebody_table_retry(const WbTableArgs *args, double *lds, bool rejected) {
+  const WbTableArgs &a = *args;
+  bool inside;
+  const PlacePtrs index_only{a.pp.order, nullptr, nullptr, nullptr, nullptr}; // (the first attempt wrote identity_out)
+  const int64_t i = placed_index(index_only, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4), a.B, inside);
+  const PlacePtrs cold{a.pp.order, a.pp.iterations, nullptr, nullptr, nullptr};
+  (void)wholebody_robot<kPerLeg, false>(*a.Pp, a.W, a.s, i, rejected, a.tau, a.grf, a.status, cold, lds);
+  if (rejected && (threadIdx.x & 15) == 0 && a.pp.working_set) a.pp.working_set[i] = 0ull; // (its slot of the table holds 0 already)
+  __builtin_amdgcn_endpgm();
+}
+template <bool kPerLeg>
+__global__ __launch_bounds__(64, 2) void wholebody_table_kernel(const DeviceParams *__restrict__ Pp, const coop::WbParamsDev W,
+                                                             const WbPtrs s, int64_t B, double *__restrict__ tau_out,
+                                                             double *__restrict__ grf_out, int32_t *__restrict__ status_out,
+                                                             const PlacePtrs pp, unsigned long long *__restrict__ set_memory) {
+  __shared__ double lds[kWbLdsDoubles];
+  bool live;
+  const int64_t i = placed_index(pp, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4), B, live);
+  const bool rejected = wholebody_robot<kPerLeg, true, true>(*Pp, W, s, i, live, tau_out, grf_out, status_out, pp, lds, set_memory);
+  if (__builtin_expect(Pp->warm_fallback && __builtin_amdgcn_ballot_w64(rejected) != 0ull, 0)) {
+    __syncthreads();
+    wholebody_table_retry<kPerLeg>(coop::kernel_arguments_again<WbTableArgs>(), lds, rejected);
+  }
+}
+
+using WbTableLayout = KernargLayout<decltype(&wholebody_table_kernel<false>)>;
+QL_KERNARG_MIRROR(WbTableLayout, WbTableArgs, true, Pp, W, s, B, tau, grf, status, pp, set_memory);
+static_assert(std::is_same<decltype(&wholebody_table_kernel<false>), decltype(&wholebody_table_kernel<true>)>::value,
+              "every instantiation of wholebody_table_kernel takes the same parameters");
 
 using WbSolveLayout = KernargLayout<decltype(&wholebody_solve_kernel<false, true>)>;
 QL_KERNARG_MIRROR(WbSolveLayout, WbSolveArgs, true, Pp, W, s, B, tau, grf, status, pp);
@@ -559,9 +612,11 @@ int qlamd_wholebody_dynamics_batch(qlamd_context *ctx, const qlamd_wholebody_bat
   return sg.finish(st);
 }
 
-int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params *params,
-                                const qlamd_wholebody_batch *in, int64_t batch, double *joint_effort,
-                                double *contact_force, int32_t *status, int memory, void *stream) {
+// The whole-body step behind its two entries.  placement: the placed entry's (checked), or NULL: the one pending on the context, if
+// any, is taken; set_memory: the placed entry's table or NULL
+static int wholebody_solve_impl(qlamd_context *ctx, const qlamd_wholebody_params *params, const qlamd_wholebody_batch *in,
+                                int64_t batch, const qlamd_placement *placement, bool placed_entry, unsigned long long *set_memory,
+                                double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream) {
   if (!ctx || !in || batch < 0 || !joint_effort || !status) return QLAMD_ERR_INVALID_ARGUMENT;
   if (!params) return QLAMD_ERR_NOT_LOADED;
   if (!in->joint_position || !in->joint_velocity || !in->base_orientation || !in->base_linear_velocity ||
@@ -575,7 +630,14 @@ int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params
   QL_ENTER(ctx, st);
   PlacePtrs pp;
   qlamd_placement pl;
-  { const int rc = take_placement(ctx, memory, batch, &pp, &pl); if (rc != QLAMD_OK) return rc; }
+  if (placed_entry) {
+    pp = PlacePtrs{};
+    pp.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
+    memset(&pl, 0, sizeof(pl));
+    if (placement) { const int rc = use_placement(*placement, memory, batch, set_memory != nullptr, &pp, &pl); if (rc != QLAMD_OK) return rc; }
+  } else {
+    const int rc = take_placement(ctx, memory, batch, &pp, &pl); if (rc != QLAMD_OK) return rc;
+  }
   const size_t B = (size_t)batch;
   WbPtrs s{in->joint_position, in->joint_velocity, in->base_orientation, in->base_linear_velocity,
            in->base_angular_velocity, in->desired_base_acceleration, in->desired_joint_acceleration, in->support_leg,
@@ -591,7 +653,10 @@ int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params
   const bool warm = pp.prev_working_set || pp.working_set;
 #define QL_LAUNCH_WB(PERLEG)                                                                                                   \
   do {                                                                                                                         \
-    if (warm)                                                                                                                  \
+    if (set_memory)                                                                                                            \
+      hipLaunchKernelGGL((wholebody_table_kernel<PERLEG>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,            \
+                         joint_effort, contact_force, status, pp, set_memory);                                                 \
+    else if (warm)                                                                                                             \
       hipLaunchKernelGGL((wholebody_solve_kernel<PERLEG, true>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,      \
                          joint_effort, contact_force, status, pp);                                                             \
     else                                                                                                                       \
@@ -604,6 +669,26 @@ int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   { const int rc = finish_placement(ctx, pl, batch, st); if (rc != QLAMD_OK) return rc; }
   return sg.finish(st);
+}
+
+int qlamd_wholebody_solve_batch(qlamd_context *ctx, const qlamd_wholebody_params *params,
+                                const qlamd_wholebody_batch *in, int64_t batch, double *joint_effort,
+                                double *contact_force, int32_t *status, int memory, void *stream) {
+  return wholebody_solve_impl(ctx, params, in, batch, nullptr, false, nullptr, joint_effort, contact_force, status, memory, stream);
+}
+
+int qlamd_wholebody_solve_placed_batch(qlamd_context *ctx, const qlamd_wholebody_params *params,
+                                       const qlamd_wholebody_batch *in, int64_t batch, const qlamd_placement *placement,
+                                       uint64_t *set_memory, double *joint_effort, double *contact_force, int32_t *status,
+                                       int memory, void *stream) {
+  // device memory only (the placement's arrays and the table are device arrays); the table is the robots' 32-byte rows and takes
+  // the place of prev_working_set; the balance step's 32-bit table has no meaning here
+  if (memory != QLAMD_MEM_DEVICE) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (placement && (!placement_ok(*placement) || placement->set_memory)) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (set_memory && ((reinterpret_cast<uintptr_t>(set_memory) & 31u) || (placement && placement->prev_working_set)))
+    return QLAMD_ERR_INVALID_ARGUMENT;
+  return wholebody_solve_impl(ctx, params, in, batch, placement, true, reinterpret_cast<unsigned long long *>(set_memory),
+                              joint_effort, contact_force, status, memory, stream);
 }
 
 } // extern "C"

@@ -170,7 +170,8 @@ class RosBalanceController {
                         hw_.orientation, hw_.linear_velocity, hw_.angular_velocity, contact_, limb_state_, store_flag_,
                         stored_joint_position_.data(), leg_mode_, support_, pid_error_last_.data(), pid_error_integral_.data(),
                         hw_.joint_effort_write, leg_state_code_, &status, &message_status, command_.data(),
-                        warm_start_ ? &working_set_ : nullptr};
+                        (warm_start_ && !set_memory_on_) ? &working_set_ : nullptr};
+    if (set_memory_on_) io.set_memory = set_memory_; // (a host-memory tick stages the table: no alignment asked of it)
     if (qlamd_full_tick_batch(ctx_->get(), &sp, &pid, &io, period, 1, 1, QLAMD_MEM_HOST, nullptr) != QLAMD_OK) return false;
     return message_status == QLAMD_WIRE_OK && status == QLAMD_STATUS_OK;
   }
@@ -178,6 +179,9 @@ class RosBalanceController {
   // plugin's other state; qlamd_tick_batch::working_set) instead of from scratch, as OOQP does in the reference.  Efforts agree
   // to the solver's accuracy; off by default.
   void setWarmStart(bool on) { warm_start_ = on; working_set_ = 0u; }
+  // ... or from the working set the robot ended with THE LAST TIME IT STOOD ON THESE SUPPORT LEGS (four words,
+  // qlamd_tick_batch::set_memory, in the place of the one word above): for a controller that drives a gait.  Off by default.
+  void setSetMemory(bool on) { set_memory_on_ = on; for (uint32_t &w : set_memory_) w = 0u; }
   const int8_t *legStateCodes() const { return leg_state_code_; }
   const int8_t *limbStates() const { return limb_state_; }
 
@@ -218,6 +222,8 @@ class RosBalanceController {
   std::vector<uint8_t> command_; // opaque command block of qlamd_full_tick_batch (batch 1)
   uint32_t working_set_ = 0u;    // final working set of the last tick's force QP (setWarmStart)
   bool warm_start_ = false;
+  uint32_t set_memory_[4] = {0u, 0u, 0u, 0u}; // a working set per support set (setSetMemory)
+  bool set_memory_on_ = false;
   double phase_[4] = {0, 0, 0, 0};
   uint8_t support_leg_[4] = {1, 1, 1, 1}, contact_[4] = {1, 1, 1, 1}, store_flag_[4] = {0, 0, 0, 0}, support_[4] = {1, 1, 1, 1};
   uint8_t leg_mode_[4] = {0, 0, 0, 0};
