@@ -411,6 +411,46 @@ int qlamd_force_distribution_placed_batch(qlamd_context *ctx, const double *join
                                           const double *virtual_wrench, int64_t batch, const qlamd_placement *placement,
                                           double *joint_effort, double *contact_force, int32_t *status, int memory,
                                           void *stream);
+/* ---- controller parameters that differ per robot -------------------------------------------------------------
+ * A batch is a simulation farm, a Monte-Carlo run or a gain sweep: friction coefficient, payload, torque limit or gains differ
+ * from robot to robot.  The reference keeps these values as state of the controller object, not as constants
+ * (legInfos_[leg].frictionCoefficient_, getFrictionCoefficient, setToInterpolated between two distributions:
+ * ContactForceDistribution.cpp:316-325,655-695,788,875); a context holds ONE set, folded into one block that every kernel reads
+ * through scalar loads.  qlamd_balance_solve_robot_params_batch takes one FOLDED record per robot instead: the values that
+ * qlamd_context_create derives from a qlamd_balance_params, minus what stays with the context -- the robot model, `gravity`
+ * and the options.  32 doubles = 256 bytes = two 128-byte lines per robot, fetched by the robot's 16 lanes with their first
+ * loads (664 bytes read per robot and step instead of 408). */
+#define QLAMD_ROBOT_PARAMS_DOUBLES 32 /* (also the feature test: the version number did not move with this entry) */
+typedef struct qlamd_robot_params {
+  double kp_trans[3], kd_trans[3], kff_trans[3], kp_rot[3], kd_rot[3], kff_rot[3];
+  double force_weights[6];
+  double regularizer, friction, min_normal_force, torque_limit;
+  double gravity_force_scale;   /* grav_comp_percentage * (torso_mass + sum leg_mass) */
+  double gravity_torque_arm[3]; /* grav_comp_percentage * (torso_mass * com_in_base + sum_l leg_mass[l] * (hip_in_base[l] - com_in_base)) */
+} qlamd_robot_params;
+/* Folds `count` parameter structs into `count` records, with the arithmetic qlamd_context_create applies to its own (one
+ * piece of code): a record filled from a context's parameters holds that context's values bit for bit, and the entry below
+ * then returns what qlamd_balance_solve_placed_batch returns, bit for bit.  params[i].gravity is IGNORED: gravity is the
+ * context's (so are the robot model and every option).  A host function: no device, no context.
+ * QLAMD_ERR_INVALID_ARGUMENT for a NULL pointer or a negative count. */
+int qlamd_robot_params_fill(const qlamd_balance_params *params, int64_t count, qlamd_robot_params *out);
+/* qlamd_balance_solve_placed_batch with robot i solved under robot_params[i] ([B] records, 16-byte aligned, in the memory space
+ * of the call) in place of the context's controller parameters.  Outputs, statuses, QLAMD_OPT_ON_FAILURE,
+ * QLAMD_OPT_WARM_FALLBACK and the counters as there.  Taken: placement = NULL; robot_order and iterations; prev_working_set /
+ * working_set; set_memory; surface_normal NULL or given; all of these with QLAMD_MEM_DEVICE, the cold forms also with
+ * QLAMD_MEM_HOST (the records are staged like the other inputs; host calls refuse a warm start as everywhere).  Every batch
+ * size runs the two-wavefront form of the kernel (at most 256 registers); the 168-register form that the other entries take
+ * from 16 384 robots up has no per-robot counterpart.
+ * Refused with QLAMD_ERR_INVALID_ARGUMENT, nothing written: robot_params == NULL; qlamd_set_robots_per_wave(16 | 64);
+ * qlamd_placement::prev_iterations / next_robot_order (these kernels carry no placement wavefronts: make the next placement
+ * with qlamd_placement_from_iterations from `iterations`); QLAMD_OPT_STATE_LAYOUT = QLAMD_STATE_RECORDS with QLAMD_MEM_DEVICE
+ * (per-field arrays only).
+ * Out of scope: a friction coefficient per LEG (the reference's legInfos_), a leg model per robot, and the whole-tick,
+ * whole-body and force-distribution entries, which keep the context's parameters. */
+int qlamd_balance_solve_robot_params_batch(qlamd_context *ctx, const qlamd_state_batch *in, const qlamd_robot_params *robot_params,
+                                           int64_t batch, const qlamd_placement *placement, double *joint_effort,
+                                           double *contact_force, int32_t *status, int memory, void *stream);
+
 /* The same for the other entries that run a lane-cooperative active-set QP -- qlamd_qp_solve_batch,
  * qlamd_weighted_lsq_qp_batch, qlamd_wholebody_solve_batch -- without a second set of signatures: the placement is handed to
  * the context and taken (and cleared) by the NEXT call of one of these three on it, whichever it is.  QLAMD_MEM_DEVICE

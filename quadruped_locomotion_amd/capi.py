@@ -31,7 +31,7 @@ EXPORTS = (
     "qlamd_full_tick_batch", "qlamd_set_option", "qlamd_tick_command_bytes", "qlamd_weighted_lsq_qp_batch",
     "qlamd_reserve", "qlamd_balance_solve_placed_batch", "qlamd_force_distribution_placed_batch",
     "qlamd_placement_from_iterations", "qlamd_place_next_call", "qlamd_get_counter", "qlamd_set_memory_slot",
-    "qlamd_wholebody_solve_placed_batch",
+    "qlamd_wholebody_solve_placed_batch", "qlamd_robot_params_fill", "qlamd_balance_solve_robot_params_batch",
 )
 
 
@@ -44,6 +44,20 @@ class BalanceParams(C.Structure):
         ("torque_limit", C.c_double), ("torso_mass", C.c_double), ("leg_mass", C.c_double * 4),
         ("gravity", C.c_double), ("grav_comp_percentage", C.c_double),
         ("com_in_base", C.c_double * 3), ("hip_in_base", (C.c_double * 3) * 4),
+    ]
+
+
+ROBOT_PARAMS_DOUBLES = 32
+
+
+class RobotParams(C.Structure):
+    """qlamd_robot_params: the folded controller parameters of one robot, ROBOT_PARAMS_DOUBLES doubles"""
+    _fields_ = [
+        ("kp_trans", C.c_double * 3), ("kd_trans", C.c_double * 3), ("kff_trans", C.c_double * 3),
+        ("kp_rot", C.c_double * 3), ("kd_rot", C.c_double * 3), ("kff_rot", C.c_double * 3),
+        ("force_weights", C.c_double * 6),
+        ("regularizer", C.c_double), ("friction", C.c_double), ("min_normal_force", C.c_double),
+        ("torque_limit", C.c_double), ("gravity_force_scale", C.c_double), ("gravity_torque_arm", C.c_double * 3),
     ]
 
 
@@ -214,6 +228,11 @@ def lib():
             L.qlamd_placement_from_iterations.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
                                                           C.c_void_p]
             L.qlamd_place_next_call.argtypes = [C.c_void_p, C.POINTER(Placement)]
+        if hasattr(L, "qlamd_robot_params_fill"):  # (absent from builds before per-robot parameters, which the probes run)
+            L.qlamd_robot_params_fill.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+            L.qlamd_balance_solve_robot_params_batch.argtypes = [C.c_void_p, C.POINTER(StateBatch), C.c_void_p, C.c_int64,
+                                                                 C.POINTER(Placement), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                 C.c_int, C.c_void_p]
         if hasattr(L, "qlamd_set_memory_slot"):  # (absent from builds before 0.7, which tools/set_memory_probe.py --lib runs)
             L.qlamd_set_memory_slot.argtypes = [C.c_uint]
             L.qlamd_set_memory_slot.restype = C.c_uint
@@ -277,6 +296,20 @@ def default_params():
     p = BalanceParams()
     lib().qlamd_balance_default_params(C.byref(p))
     return p
+
+
+def robot_params_fill(params):
+    """qlamd_robot_params_fill: a BalanceParams, a list of them or a ctypes array of them -> numpy float64 [B, 32], one folded
+    record per robot (row i viewed as a RobotParams: RobotParams.from_buffer(records[i])).  `gravity` is not part of a record:
+    it stays the context's.  A host function: no device is needed."""
+    if isinstance(params, BalanceParams):
+        params = [params]
+    arr = params if isinstance(params, C.Array) else (BalanceParams * len(params))(*params)
+    out = np.zeros((len(arr), ROBOT_PARAMS_DOUBLES), dtype=np.float64)
+    rc = lib().qlamd_robot_params_fill(C.addressof(arr) if len(arr) else None, len(arr), out.ctypes.data if len(arr) else None)
+    if rc != OK and len(arr):
+        raise QlamdError(rc, "qlamd_robot_params_fill")
+    return out
 
 
 def default_pose_params():
@@ -427,6 +460,65 @@ class Context:
                                                          C.c_void_p(stream) if stream else None)
         if rc != OK:
             raise QlamdError(rc, "qlamd_force_distribution_placed_batch")
+
+    def balance_solve_robot_params_device(self, dstate, robot_params, tau, grf, status, order=None, iterations=None,
+                                          prev_iterations=None, next_order=None, policy=0, stream=None, prev_working_set=None,
+                                          working_set=None, set_memory=None):
+        """qlamd_balance_solve_robot_params_batch on torch CUDA tensors: robot_params = float64 [B, 32], robot i's folded record
+        (robot_params_fill) in row i; the other arguments as balance_solve_placed_device (prev_iterations / next_order are
+        passed on for the library to refuse).  Asynchronous."""
+        sb = StateBatch()
+        B = dstate["q"].shape[0]
+        for key, field, _ in FIELD_OF_KEY:
+            setattr(sb, field, dstate[key].data_ptr())
+        sb.support_leg = dstate["stance"].data_ptr()
+        if dstate.get("normals") is not None:
+            sb.surface_normal = dstate["normals"].data_ptr()
+        if robot_params is not None and (str(robot_params.dtype) != "torch.float64" or robot_params.numel() != ROBOT_PARAMS_DOUBLES * B or
+                                         not robot_params.is_contiguous()):
+            raise ValueError("robot_params must be a contiguous float64 tensor of %d x %d elements" % (B, ROBOT_PARAMS_DOUBLES))
+        for name, t in (("order", order), ("iterations", iterations), ("prev_iterations", prev_iterations), ("next_order", next_order),
+                        ("prev_working_set", prev_working_set), ("working_set", working_set)):
+            if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != B or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous int32 tensor of %d elements" % (name, B))
+        _check_set_memory(set_memory, B)
+        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
+                       _ptr(prev_working_set), _ptr(working_set), _ptr(set_memory))
+        rc = lib().qlamd_balance_solve_robot_params_batch(self._h, C.byref(sb), _ptr(robot_params), B, C.byref(pl), tau.data_ptr(),
+                                                          grf.data_ptr() if grf is not None else None, status.data_ptr(),
+                                                          MEM_DEVICE, C.c_void_p(stream) if stream else None)
+        if rc != OK:
+            raise QlamdError(rc, "qlamd_balance_solve_robot_params_batch")
+
+    def balance_solve_robot_params_host(self, state, robot_params, order=None, normals=None, want_forces=True):
+        """qlamd_balance_solve_robot_params_batch with host (numpy) buffers: robot_params float64 [B, 32] -> (tau, grf, status,
+        iterations)."""
+        B = int(np.asarray(state["q"]).reshape(-1, 12).shape[0])
+        sb, keep = StateBatch(), []
+        for key, field, k in FIELD_OF_KEY:
+            a = np.ascontiguousarray(np.asarray(state[key], dtype=np.float64).reshape(B, k))
+            keep.append(a)
+            setattr(sb, field, a.ctypes.data)
+        st = np.ascontiguousarray(np.asarray(state["stance"], dtype=np.uint8).reshape(B, 4))
+        sb.support_leg = st.ctypes.data
+        if normals is not None:
+            nw = np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(B, 12))
+            keep.append(nw)
+            sb.surface_normal = nw.ctypes.data
+        if order is not None:
+            order = np.ascontiguousarray(np.asarray(order, dtype=np.int32).reshape(B))
+        if robot_params is not None:
+            robot_params = np.ascontiguousarray(np.asarray(robot_params, dtype=np.float64).reshape(B, ROBOT_PARAMS_DOUBLES))
+        tau = np.zeros((B, 12))
+        grf = np.zeros((B, 12)) if want_forces else None
+        status = np.full(B, -1, dtype=np.int32)
+        iters = np.full(B, -1, dtype=np.int32)
+        pl = Placement(_ptr(order), iters.ctypes.data)
+        rc = lib().qlamd_balance_solve_robot_params_batch(self._h, C.byref(sb), _ptr(robot_params), B, C.byref(pl), tau.ctypes.data,
+                                                          grf.ctypes.data if want_forces else None, status.ctypes.data, MEM_HOST, None)
+        if rc != OK:
+            raise QlamdError(rc, "qlamd_balance_solve_robot_params_batch")
+        return tau, grf, status, iters
 
     def balance_solve_placed_host(self, state, order=None, normals=None, want_forces=True, prev_iterations=None, policy=0):
         """qlamd_balance_solve_placed_batch with host (numpy) buffers -> (tau, grf, status, iterations[, next_order])."""

@@ -110,13 +110,33 @@ constexpr int kCoopNrmDoubles = 12 * 64; // 5 row kinds + parked Jacobian row (3
 // takes the 12-variable form, which gives a robot on two legs the same result bit for bit (its padding rows add exact zeros)
 // kTable (with kWarm): the set a robot starts from is the word of its support set in s.set_memory's four, and its final set
 // goes back there -- the set it ended with the last time it stood on these legs, not the one of the step before
+// kRobotParams (balance_robot_params_kernel): the controller parameters are the robot's own -- its record of
+// QLAMD_ROBOT_PARAMS_DOUBLES doubles in robot_params [B] (qlamd_robot_params: the head of DeviceParams, folded per robot) --
+// instead of the context's.  The row's 16 lanes fetch the 256 bytes with the first loads, two doubles a lane, and stage them
+// in lds_rp, the row's 32 doubles of LDS; every value is read from there where the context's is read as a scalar operand
+// (replicated in the row by construction), so none of them is live longer than the context's would be in a register of its
+// own: the gains in the wrench segment only, the weights up to the row of G, the torque limit fetched at the clamp.  The leg
+// model table, gravity and the options stay the context's.
+constexpr int kRpKpT = 0, kRpKdT = 3, kRpKffT = 6, kRpKpR = 9, kRpKdR = 12, kRpKffR = 15, kRpS = 18, kRpWreg = 24, kRpMu = 25,
+              kRpFmin = 26, kRpTauMax = 27, kRpFgScale = 28, kRpTgArm = 29;
+static_assert(kRpTgArm + 3 == QLAMD_ROBOT_PARAMS_DOUBLES, "the record ends with the gravity torque arm");
 template <bool kPerLeg, int kBlock = 64, bool kWarm = false, bool kParkInputs = false, bool kThroughput = false, bool kSmallForm = true,
-          bool kTable = false>
+          bool kTable = false, bool kRobotParams = false>
 __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs &s, int64_t irobot, bool robot_live_in,
                                            double *lds_tab, double *lds_row, double *lds_nrm,
                                            double *__restrict__ tau_out,
-                                           double *__restrict__ grf_out, int32_t *__restrict__ status_out, bool cold = false) {
+                                           double *__restrict__ grf_out, int32_t *__restrict__ status_out, bool cold = false,
+                                           const double *__restrict__ robot_params = nullptr, double *lds_rp = nullptr) {
   bool robot_live = robot_live_in;
+  // a controller parameter: the robot's own (entry k of its staged record) or the context's
+  const auto prm = [&](int k, const double &of_context) -> double {
+    if constexpr (kRobotParams) return lds_rp[k];
+    else return of_context;
+  };
+  const auto prm_vec = [&](int k, const double *of_context) -> const double * {
+    if constexpr (kRobotParams) return lds_rp + k;
+    else return of_context;
+  };
   const int lr = threadIdx.x & 15;   // lane in row
   const int leg = lr >> 2, c = lr & 3; // leg: my SLOT in the row (the leg behind it: aleg, below)
   const bool comp = c < 3;           // carries a variable / matrix row
@@ -161,6 +181,8 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
   const uint32_t sm = *reinterpret_cast<const uint32_t *>(s.stance + kSB * i_in);
   double qj = s.q[kS12 * i_in + (comp ? myidx : 0)];
   const uint8_t alive = s.live ? s.live[i_in] : (uint8_t)1;
+  double2 rpv = make_double2(0.0, 0.0); // my two doubles of the robot's parameter record
+  if constexpr (kRobotParams) rpv = reinterpret_cast<const double2 *>(robot_params + QLAMD_ROBOT_PARAMS_DOUBLES * i_in)[lr];
   unsigned warm_set = 0u;
   bool build_set = false;
   static_assert(!kTable || kWarm, "the table is a warm start");
@@ -217,6 +239,7 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
     const int idx = (int)threadIdx.x + kBlock * j;
     if (idx < 4 * kTabPerLeg) lds_tab[idx] = tabv[j];
   }
+  if constexpr (kRobotParams) reinterpret_cast<double2 *>(lds_rp)[lr] = rpv;
   __syncthreads();
 
   QL_STAMP(1); QL_QP_BLOCK_STAMP(4);
@@ -280,21 +303,22 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
       }
       // VirtualModelController.cpp:208-231 (vertical P and D enter twice), as virtual_wrench()
       const double ff[3] = {in.dlinvel[0], in.dlinvel[1], 0.0};
-      const double gfb[3] = {0.0, 0.0, P.kp_t[2] * e_p[2]};
-      const double gdb[3] = {0.0, 0.0, P.kd_t[2] * e_v[2]};
+      const double gfb[3] = {0.0, 0.0, prm(kRpKpT + 2, P.kp_t[2]) * e_p[2]};
+      const double gdb[3] = {0.0, 0.0, prm(kRpKdT + 2, P.kd_t[2]) * e_v[2]};
       double Rep[3], Rev[3], Rff[3], fbp[3], fbd[3];
       irot(Rm, e_p, Rep); irot(Rm, e_v, Rev); irot(Rm, ff, Rff); irot(Rm, gfb, fbp); irot(Rm, gdb, fbd);
 #pragma unroll
       for (int k = 0; k < 3; k++)
-        b[k] = P.kp_t[k] * Rep[k] + P.kd_t[k] * Rev[k] + P.kff_t[k] * Rff[k] - P.Fg_scale * gB[k] + fbp[k] + fbd[k];
+        b[k] = prm(kRpKpT + k, P.kp_t[k]) * Rep[k] + prm(kRpKdT + k, P.kd_t[k]) * Rev[k] + prm(kRpKffT + k, P.kff_t[k]) * Rff[k] -
+               prm(kRpFgScale, P.Fg_scale) * gB[k] + fbp[k] + fbd[k];
       // VirtualModelController.cpp:244-259
-      const double kdw[3] = {P.kd_r[0] * e_w[0], P.kd_r[1] * e_w[1], P.kd_r[2] * e_w[2]};
-      const double kfw[3] = {0.0, 0.0, P.kff_r[2] * in.dangvel[2]};
+      const double kdw[3] = {prm(kRpKdR, P.kd_r[0]) * e_w[0], prm(kRpKdR + 1, P.kd_r[1]) * e_w[1], prm(kRpKdR + 2, P.kd_r[2]) * e_w[2]};
+      const double kfw[3] = {0.0, 0.0, prm(kRpKffR + 2, P.kff_r[2]) * in.dangvel[2]};
       double Rd[3], Rf[3], Tg[3];
       irot(Rm, kdw, Rd); irot(Rm, kfw, Rf);
-      cross3(P.Tg_arm, gB, Tg);
+      cross3(prm_vec(kRpTgArm, P.Tg_arm), gB, Tg);
 #pragma unroll
-      for (int k = 0; k < 3; k++) b[3 + k] = P.kp_r[k] * (-wr_k * wr_d[k]) + Rd[k] + Rf[k] - Tg[k];
+      for (int k = 0; k < 3; k++) b[3 + k] = prm(kRpKpR + k, P.kp_r[k]) * (-wr_k * wr_d[k]) + Rd[k] + Rf[k] - Tg[k];
     }
   }
 
@@ -368,7 +392,7 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
     if (s2 >= 1e-12) k = 2.0 * acos(wr_dw) / sqrt(s2);
     const double dk = wr_slow ? k - wr_k : 0.0;
 #pragma unroll
-    for (int a = 0; a < 3; a++) b[3 + a] -= P.kp_r[a] * dk * wr_d[a];
+    for (int a = 0; a < 3; a++) b[3 + a] -= prm(kRpKpR + a, P.kp_r[a]) * dk * wr_d[a];
   }
   if (s.wrench) {
 #pragma unroll
@@ -411,7 +435,7 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
     t2[0] *= nn; t2[1] *= nn; t2[2] *= nn;
     myn = pick3(nb, c); myt1 = pick3(t1, c); myt2 = pick3(t2, c);
   }
-  const double mu = P.mu, f_min = P.f_min;
+  const double mu = prm(kRpMu, P.mu), f_min = prm(kRpFmin, P.f_min);
 
   QL_STAMP(4);
   QL_STAMP(5);
@@ -435,9 +459,9 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
       double b_l[6];
 #pragma unroll
       for (int k = 0; k < 6; k++) b_l[k] = lds_tab[64 + 6 * (((int)threadIdx.x & 63) >> 4) + k];
-      force_qp_objective(P.S, P.w_reg, foot_l, stance_slots, comp && on, b_l, nullptr, 0.0, Q.Gm, Q.g0);
+      force_qp_objective(prm_vec(kRpS, P.S), prm(kRpWreg, P.w_reg), foot_l, stance_slots, comp && on, b_l, nullptr, 0.0, Q.Gm, Q.g0);
     } else {
-      force_qp_objective(P.S, P.w_reg, foot, stance_slots, comp && on, b, nullptr, 0.0, Q.Gm, Q.g0);
+      force_qp_objective(prm_vec(kRpS, P.S), prm(kRpWreg, P.w_reg), foot, stance_slots, comp && on, b, nullptr, 0.0, Q.Gm, Q.g0);
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) { Q.nb[k] = nb[k]; Q.t1[k] = t1[k]; Q.t2[k] = t2[k]; }
@@ -492,8 +516,9 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
     const double t1 = quad_sum(sel(comp, Jr[1] * fx, 0.0)) + Gr[1];
     const double t2 = quad_sum(sel(comp, Jr[2] * fx, 0.0)) + Gr[2];
     double t = sel(c == 0, t0, sel(c == 1, t1, t2));
-    t = t > P.tau_max ? P.tau_max : t;
-    t = t < -P.tau_max ? -P.tau_max : t;
+    const double tau_max = prm(kRpTauMax, P.tau_max);
+    t = t > tau_max ? tau_max : t;
+    t = t < -tau_max ? -tau_max : t;
     if (comp && robot_live && !(P.keep_on_failure && status != kStatusOk) && (on || !s.support_only)) {
       tau_out[12 * i + aidx] = live ? t : 0.0;
       if (grf_out) grf_out[12 * i + aidx] = live ? x : 0.0;

@@ -560,6 +560,73 @@ QL_KERNARG_MIRROR(CoopKernelLayout, BalanceCoopArgs, true, Pp, s, B, tau, grf, s
 static_assert(std::is_same<decltype(&balance_coop_kernel<false, 2, true, true>), decltype(&balance_table_kernel<true, 3>)>::value,
               "balance_table_kernel takes the parameters of balance_coop_kernel");
 
+// Controller parameters per robot (qlamd_balance_solve_robot_params_batch): the body of coop_robot with every parameter of the
+// controller taken from the robot's own record (robot_params [B] of QLAMD_ROBOT_PARAMS_DOUBLES doubles) instead of *Pp, whose
+// leg model table, gravity and options still hold.  Kernels of their own -- one more parameter, 1 KB more LDS (the four rows'
+// staged records, behind the block of the other kernels) -- so that a launch without per-robot parameters runs what it ran
+// before they existed.  Always the two-wavefront form, always with a placement's robot_order (NULL: the batch order) and the
+// 6-variable form for wavefronts whose robots stand on two legs (results bit for bit those of the 12-variable form); no shadow
+// wavefronts: the entry refuses prev_iterations / next_robot_order.
+constexpr int kRobotParamsLdsTotal = kCoopLdsTotal + 4 * kCoopWaves * QLAMD_ROBOT_PARAMS_DOUBLES;
+static_assert(kCoopWaves == 1, "balance_robot_params_kernel is written for one wavefront per workgroup");
+static_assert(kCoopLdsTotal % 2 == 0, "the staged records start on a 16-byte boundary");
+static_assert(2 * 4 * kRobotParamsLdsTotal * sizeof(double) <= 160 * 1024, "two wavefronts per SIMD fit a compute unit's LDS");
+static_assert(sizeof(qlamd_robot_params) == QLAMD_ROBOT_PARAMS_DOUBLES * sizeof(double) && QLAMD_ROBOT_PARAMS_DOUBLES == 2 * 16,
+              "a row's 16 lanes fetch the record two doubles each");
+struct RobotParamsArgs { const DeviceParams *Pp; StatePtrs s; int64_t B; double *tau, *grf; int32_t *status; const double *robot_params; };
+template <bool kPerLeg, bool kWarm, bool kTable>
+__device__ __forceinline__ bool robot_params_rows(const DeviceParams &P, const StatePtrs &s, int64_t B, double *tau, double *grf,
+                                                  int32_t *status, const double *robot_params, double *lds, bool cold, bool only) {
+  double *tab = lds, *rows = lds + 4 * kTabPerLeg, *nrm = rows + 4 * coop::kCoopLdsDoubles, *rp = lds + kCoopLdsTotal;
+  const int row = threadIdx.x >> 4;
+  int64_t i = (int64_t)blockIdx.x * 4 + row;
+  bool live = i < B;
+  if (!live) i = B - 1;
+  if (s.order) {
+    const int64_t o = s.order[i];
+    live = live && o >= 0 && o < B;
+    i = live ? o : B - 1;
+  }
+  const coop::CoopPtrs cp{s.q, s.pos, s.quat, s.linvel, s.angvel, s.dpos, s.dquat, s.dlinvel, s.dangvel, s.stance,
+                          s.normals, nullptr, nullptr, 0, s.iterations, kWarm ? s.prev_working_set : nullptr,
+                          kWarm ? s.working_set : nullptr, kWarm ? s.warm_retries : nullptr, 0, kTable ? s.set_memory : nullptr};
+  return coop::coop_robot<kPerLeg, 64, kWarm, false, false, true, kTable, true>(
+      P, cp, i, live && only, tab, rows + row * coop::kCoopLdsDoubles, nrm, tau, grf, status, cold, robot_params,
+      rp + row * QLAMD_ROBOT_PARAMS_DOUBLES);
+}
+// the second attempt of its rejected rows (as balance_cold_retry: a function that ends the wavefront, one per calling kernel)
+template <bool kPerLeg, bool kTable>
+__device__ __attribute__((noinline, noreturn)) void balance_robot_params_retry(const RobotParamsArgs *args, double *lds, bool rejected) {
+  const RobotParamsArgs &a = *args;
+  (void)robot_params_rows<kPerLeg, false, false>(*a.Pp, a.s, a.B, a.tau, a.grf, a.status, a.robot_params, lds, true, rejected);
+  if (rejected && (threadIdx.x & 15) == 0 && a.s.working_set) {
+    // (the rejected row's robot, as robot_params_rows found it)
+    int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4);
+    if (a.s.order) i = a.s.order[i];
+    a.s.working_set[i] = 0u;
+  }
+  __builtin_amdgcn_endpgm();
+}
+template <bool kPerLeg, bool kWarm, bool kTable>
+__global__ __launch_bounds__(64, 2) void balance_robot_params_kernel(const DeviceParams *__restrict__ Pp, const StatePtrs s, int64_t B,
+                                                                     double *__restrict__ tau, double *__restrict__ grf,
+                                                                     int32_t *__restrict__ status,
+                                                                     const double *__restrict__ robot_params) {
+  __shared__ __attribute__((aligned(16))) double lds[kRobotParamsLdsTotal]; // (the staged records are stored 16 bytes a lane)
+  const DeviceParams &P = *Pp;
+  const bool rejected = robot_params_rows<kPerLeg, kWarm, kTable>(P, s, B, tau, grf, status, robot_params, lds, false, true);
+  if constexpr (kWarm) {
+    if (__builtin_expect(P.warm_fallback && __builtin_amdgcn_ballot_w64(rejected) != 0ull, 0)) {
+      __syncthreads(); // (one wavefront: the first attempt's LDS reads are done before the table is staged again)
+      balance_robot_params_retry<kPerLeg, kTable>(coop::kernel_arguments_again<RobotParamsArgs>(), lds, rejected);
+    }
+  }
+}
+using RobotParamsKernelLayout = KernargLayout<decltype(&balance_robot_params_kernel<false, true, true>)>;
+QL_KERNARG_MIRROR(RobotParamsKernelLayout, RobotParamsArgs, true, Pp, s, B, tau, grf, status, robot_params);
+static_assert(std::is_same<decltype(&balance_robot_params_kernel<false, true, true>), decltype(&balance_robot_params_kernel<true, false, false>)>::value,
+              "every balance_robot_params_kernel has the one signature");
+
 __global__ __launch_bounds__(64) void virtual_wrench_kernel(const DeviceParams *__restrict__ Pp, const StatePtrs s,
                                                             int64_t B, double *__restrict__ wrench) {
   const DeviceParams &P = *Pp;
@@ -940,15 +1007,61 @@ int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, i
 }
 
 namespace {
-// The four public balance / force-distribution entries: the checks of their arguments, the host buffers' staging, then
-// balance_launch.  pl: the placed entries' placement (NULL otherwise), in the memory space of the call
+// One launch of balance_robot_params_kernel on device arrays (the entry has checked its arguments): cold, warm-started from
+// prev_working_set, or from the table, with or without per-leg normals -- always the two-wavefront form, whatever the batch
+int robot_params_launch(qlamd_context *ctx, const qlamd_state_batch &in, const qlamd_placement &pl, const double *d_robot_params,
+                        int64_t batch, double *d_tau, double *d_grf, int32_t *d_status, hipStream_t st) {
+  const bool table = pl.set_memory != nullptr;
+  const bool warm = pl.prev_working_set || pl.working_set || table;
+  StatePtrs s{};
+  s.q = in.joint_position; s.pos = in.base_position; s.quat = in.base_orientation;
+  s.linvel = in.base_linear_velocity; s.angvel = in.base_angular_velocity;
+  s.dpos = in.desired_position; s.dquat = in.desired_orientation;
+  s.dlinvel = in.desired_linear_velocity; s.dangvel = in.desired_angular_velocity;
+  s.stance = in.support_leg; s.normals = in.surface_normal;
+  s.order = pl.robot_order; s.iterations = pl.iterations;
+  s.prev_working_set = pl.prev_working_set;
+  s.working_set = pl.working_set;
+  s.set_memory = pl.set_memory;
+  s.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
+  const unsigned grid = (unsigned)((batch + 3) / 4);
+#define QL_LAUNCH_ROBOT_PARAMS(PERLEG)                                                                                          \
+  do {                                                                                                                          \
+    if (table)                                                                                                                  \
+      hipLaunchKernelGGL((balance_robot_params_kernel<PERLEG, true, true>), dim3(grid), dim3(64), 0, st, ctx->d_params, s, batch, \
+                         d_tau, d_grf, d_status, d_robot_params);                                                               \
+    else if (warm)                                                                                                              \
+      hipLaunchKernelGGL((balance_robot_params_kernel<PERLEG, true, false>), dim3(grid), dim3(64), 0, st, ctx->d_params, s,      \
+                         batch, d_tau, d_grf, d_status, d_robot_params);                                                        \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((balance_robot_params_kernel<PERLEG, false, false>), dim3(grid), dim3(64), 0, st, ctx->d_params, s,     \
+                         batch, d_tau, d_grf, d_status, d_robot_params);                                                        \
+  } while (0)
+  if (s.normals) QL_LAUNCH_ROBOT_PARAMS(true);
+  else QL_LAUNCH_ROBOT_PARAMS(false);
+#undef QL_LAUNCH_ROBOT_PARAMS
+  return hipGetLastError() == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
+}
+
+// The public balance / force-distribution entries: the checks of their arguments, the host buffers' staging, then
+// balance_launch.  pl: the placed entries' placement (NULL otherwise), in the memory space of the call; per_robot: the call is
+// qlamd_balance_solve_robot_params_batch and robot_params [B] its records (in the memory space of the call)
 int balance_entry(qlamd_context *ctx, const qlamd_state_batch *in_user, const double *wrench, int64_t batch, const qlamd_placement *pl,
-                  double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream) {
+                  double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream, bool per_robot = false,
+                  const qlamd_robot_params *robot_params = nullptr) {
   if (!ctx || !in_user || batch < 0 || !joint_effort || !status) return QLAMD_ERR_INVALID_ARGUMENT;
   qlamd_placement p;
   memset(&p, 0, sizeof(p));
   if (pl) p = *pl;
   if (!placement_ok(p)) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (per_robot) {
+    // records or nothing; the lane-cooperative kernels only; no placement made inside the launch (no shadow wavefronts in
+    // these kernels: qlamd_placement_from_iterations makes it); 16-byte loads of the records
+    if (!robot_params || (memory == QLAMD_MEM_DEVICE && (reinterpret_cast<uintptr_t>(robot_params) & 15u)) || pick_rpw(ctx, batch) != 4 || p.prev_iterations ||
+        p.next_robot_order || batch > INT32_MAX)
+      return QLAMD_ERR_INVALID_ARGUMENT;
+    if (memory == QLAMD_MEM_DEVICE && ctx->state_record_doubles) return QLAMD_ERR_INVALID_ARGUMENT; // (QLAMD_STATE_RECORDS: not taken)
+  }
   // the table takes the place of prev_working_set, and its robots' four words are one 16-byte load
   if (p.set_memory && (p.prev_working_set || (reinterpret_cast<uintptr_t>(p.set_memory) & 15u))) return QLAMD_ERR_INVALID_ARGUMENT;
   const bool warm = p.prev_working_set || p.working_set || p.set_memory;
@@ -1000,11 +1113,15 @@ int balance_entry(qlamd_context *ctx, const qlamd_state_batch *in_user, const do
   sg.in(in.desired_position, B * 24); sg.in(in.desired_orientation, B * 32);
   sg.in(in.desired_linear_velocity, B * 24); sg.in(in.desired_angular_velocity, B * 24);
   sg.in(in.support_leg, B * 4); sg.in(in.surface_normal, B * 96); sg.in(wrench, B * 48); sg.in(dp.robot_order, B * 4);
+  sg.in(robot_params, B * sizeof(qlamd_robot_params));
   sg.out(joint_effort, B * 96, keep); sg.out(contact_force, B * 96, keep);
   sg.out(status, B * 4); sg.out(dp.iterations, B * 4);
   int rc = sg.upload(ctx, st);
   if (rc != QLAMD_OK) return rc;
-  rc = balance_launch(ctx, in, layout, wrench, nullptr, 0, dp, batch, joint_effort, contact_force, status, st);
+  if (per_robot)
+    rc = robot_params_launch(ctx, in, dp, reinterpret_cast<const double *>(robot_params), batch, joint_effort, contact_force, status, st);
+  else
+    rc = balance_launch(ctx, in, layout, wrench, nullptr, 0, dp, batch, joint_effort, contact_force, status, st);
   if (rc == QLAMD_OK) rc = sg.finish(st);
   if (rc == QLAMD_OK && memory == QLAMD_MEM_HOST && p.next_robot_order)
     rc = qlamd_placement_from_iterations(ctx, p.prev_iterations, batch, p.policy, p.next_robot_order, QLAMD_MEM_HOST, stream);
@@ -1042,6 +1159,18 @@ int qlamd_force_distribution_batch(qlamd_context *ctx, const double *joint_posit
 int qlamd_balance_solve_placed_batch(qlamd_context *ctx, const qlamd_state_batch *in, int64_t batch, const qlamd_placement *placement,
                                      double *joint_effort, double *contact_force, int32_t *status, int memory, void *stream) {
   return balance_entry(ctx, in, nullptr, batch, placement, joint_effort, contact_force, status, memory, stream);
+}
+
+int qlamd_balance_solve_robot_params_batch(qlamd_context *ctx, const qlamd_state_batch *in, const qlamd_robot_params *robot_params,
+                                           int64_t batch, const qlamd_placement *placement, double *joint_effort,
+                                           double *contact_force, int32_t *status, int memory, void *stream) {
+  return balance_entry(ctx, in, nullptr, batch, placement, joint_effort, contact_force, status, memory, stream, true, robot_params);
+}
+
+int qlamd_robot_params_fill(const qlamd_balance_params *params, int64_t count, qlamd_robot_params *out) {
+  if (!params || !out || count < 0) return QLAMD_ERR_INVALID_ARGUMENT;
+  for (int64_t i = 0; i < count; i++) fold_robot_params(params[i], &out[i]);
+  return QLAMD_OK;
 }
 
 int qlamd_force_distribution_placed_batch(qlamd_context *ctx, const double *joint_position, const double *base_orientation,

@@ -55,26 +55,44 @@ inline void rpy_to_matrix(const double rpy[3], double R[9]) {
   R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
 }
 
-inline void build_device_params(const qlamd_balance_params &p, const qlamd_robot_model &m, DeviceParams *d) {
-  memset(d, 0, sizeof(*d));
+// The controller's part of the fold: what one qlamd_balance_params becomes for the kernels, minus what stays with the context
+// (gravity, the leg model, the options) -- the record of qlamd_robot_params_fill and, copied member by member, the head of
+// DeviceParams: one piece of arithmetic for both, so a record filled from a context's parameters holds that context's values
+// bit for bit.
+inline void fold_robot_params(const qlamd_balance_params &p, qlamd_robot_params *r) {
   for (int i = 0; i < 3; i++) {
-    d->kp_t[i] = p.kp_trans[i]; d->kd_t[i] = p.kd_trans[i]; d->kff_t[i] = p.kff_trans[i];
-    d->kp_r[i] = p.kp_rot[i];   d->kd_r[i] = p.kd_rot[i];   d->kff_r[i] = p.kff_rot[i];
+    r->kp_trans[i] = p.kp_trans[i]; r->kd_trans[i] = p.kd_trans[i]; r->kff_trans[i] = p.kff_trans[i];
+    r->kp_rot[i] = p.kp_rot[i];     r->kd_rot[i] = p.kd_rot[i];     r->kff_rot[i] = p.kff_rot[i];
   }
-  for (int i = 0; i < 6; i++) d->S[i] = p.force_weights[i];
-  d->w_reg = p.regularizer; d->mu = p.friction; d->f_min = p.min_normal_force; d->tau_max = p.torque_limit;
-  d->grav = p.gravity;
-  d->refine_passes = 1;
-  d->keep_on_failure = 0;
-  d->warm_fallback = 1;
+  for (int i = 0; i < 6; i++) r->force_weights[i] = p.force_weights[i];
+  r->regularizer = p.regularizer; r->friction = p.friction; r->min_normal_force = p.min_normal_force;
+  r->torque_limit = p.torque_limit;
   double mass = p.torso_mass;
   double arm[3] = {p.torso_mass * p.com_in_base[0], p.torso_mass * p.com_in_base[1], p.torso_mass * p.com_in_base[2]};
   for (int l = 0; l < 4; l++) {
     mass += p.leg_mass[l];
     for (int i = 0; i < 3; i++) arm[i] += p.leg_mass[l] * (p.hip_in_base[l][i] - p.com_in_base[i]);
   }
-  d->Fg_scale = p.grav_comp_percentage * mass;
-  for (int i = 0; i < 3; i++) d->Tg_arm[i] = p.grav_comp_percentage * arm[i];
+  r->gravity_force_scale = p.grav_comp_percentage * mass;
+  for (int i = 0; i < 3; i++) r->gravity_torque_arm[i] = p.grav_comp_percentage * arm[i];
+}
+
+inline void build_device_params(const qlamd_balance_params &p, const qlamd_robot_model &m, DeviceParams *d) {
+  memset(d, 0, sizeof(*d));
+  qlamd_robot_params r;
+  fold_robot_params(p, &r);
+  for (int i = 0; i < 3; i++) {
+    d->kp_t[i] = r.kp_trans[i]; d->kd_t[i] = r.kd_trans[i]; d->kff_t[i] = r.kff_trans[i];
+    d->kp_r[i] = r.kp_rot[i];   d->kd_r[i] = r.kd_rot[i];   d->kff_r[i] = r.kff_rot[i];
+  }
+  for (int i = 0; i < 6; i++) d->S[i] = r.force_weights[i];
+  d->w_reg = r.regularizer; d->mu = r.friction; d->f_min = r.min_normal_force; d->tau_max = r.torque_limit;
+  d->grav = p.gravity;
+  d->refine_passes = 1;
+  d->keep_on_failure = 0;
+  d->warm_fallback = 1;
+  d->Fg_scale = r.gravity_force_scale;
+  for (int i = 0; i < 3; i++) d->Tg_arm[i] = r.gravity_torque_arm[i];
   for (int l = 0; l < 4; l++) {
     double *tab = d->legtab + kTabPerLeg * l;
     for (int k = 0; k < 4; k++) {

@@ -375,3 +375,66 @@ def wholebody_trajectory(batch, gait="trot", ticks=1, dt=CONTROL_PERIOD, seed=SE
         s["qd"], s["a_des"] = first["qd"], first["a_des"]
         out.append(s)
     return out
+
+
+# ---- controller parameters that differ per robot (qlamd_balance_solve_robot_params_batch) -------------------------------
+# One draw per robot of every field of qlamd_balance_params but `gravity` and `hip_in_base` (the defaults: gravity is the
+# context's, the hips belong to the robot model): gains, weights and regularizer scaled by U(0.5, 2) around the reference's
+# values (balance_controller/config/controller_gains.yaml:1-41), the others uniform in ranges around theirs.  Neighbouring robots
+# differ widely -- what a test of the four robots of a wavefront wants.
+ROBOT_PARAM_DEFAULTS = dict(kp_trans=(5000.0, 5000.0, 10000.0), kd_trans=(5000.0, 4000.0, 5000.0), kff_trans=(10.0, 10.0, 100.0),
+                            kp_rot=(10000.0, 10000.0, 4000.0), kd_rot=(1000.0, 1000.0, 1000.0), kff_rot=(0.2, 0.2, 1000.0),
+                            force_weights=(1.0, 5.0, 1.0, 10.0, 10.0, 5.0), regularizer=0.0001)
+ROBOT_PARAM_SCALE = (0.5, 2.0)  # of the gains, the weights and the regularizer
+ROBOT_PARAM_RANGES = dict(friction=(0.3, 0.9), min_normal_force=(2.0, 30.0), torque_limit=(60.0, 300.0), torso_mass=(20.0, 40.0),
+                          leg_mass=(4.0, 8.0), grav_comp_percentage=(0.8, 1.0), com_in_base=(-0.03, 0.03))
+_GAIN_FIELDS = ("kp_trans", "kd_trans", "kff_trans", "kp_rot", "kd_rot", "kff_rot")
+
+
+def make_robot_params(batch, seed=SEED + 31, offset=0):
+    """Per-robot controller parameters for robots [offset, offset + batch): a dict with one float64 array per field of
+    qlamd_balance_params, [B] for a scalar field and [B, k] for an array (hip_in_base [B, 4, 3], gravity [B]: the defaults).
+    Counter based like make_states: robot i draws the same values whatever the batch."""
+    u = _uniform(seed, offset, offset + batch)
+    c = 0
+    out = {}
+    lo, hi = ROBOT_PARAM_SCALE
+    for name in _GAIN_FIELDS + ("force_weights",):
+        base = np.array(ROBOT_PARAM_DEFAULTS[name])
+        out[name] = base[None, :] * (lo + (hi - lo) * u[:, c:c + base.size])
+        c += base.size
+    out["regularizer"] = ROBOT_PARAM_DEFAULTS["regularizer"] * (lo + (hi - lo) * u[:, c])
+    c += 1
+    for name, k in (("friction", 0), ("min_normal_force", 0), ("torque_limit", 0), ("torso_mass", 0), ("leg_mass", 4),
+                    ("grav_comp_percentage", 0), ("com_in_base", 3)):
+        a, b = ROBOT_PARAM_RANGES[name]
+        out[name] = a + (b - a) * (u[:, c] if k == 0 else u[:, c:c + k])
+        c += max(k, 1)
+    assert c <= _DRAWS
+    out["gravity"] = np.full(batch, 9.8)
+    out["hip_in_base"] = np.tile(np.array([[0.42, 0.075, 0.0], [0.42, -0.075, 0.0], [-0.42, -0.075, 0.0], [-0.42, 0.075, 0.0]]),
+                                 (batch, 1, 1))
+    return {k: np.ascontiguousarray(v) for k, v in out.items()}
+
+
+ROBOT_PARAM_FIELDS = _GAIN_FIELDS + ("force_weights", "regularizer", "friction", "min_normal_force", "torque_limit", "torso_mass",
+                                      "leg_mass", "gravity", "grav_comp_percentage", "com_in_base", "hip_in_base")
+
+
+def robot_params_struct(rp, i, cls):
+    """Row i of a make_robot_params dict as a parameter structure: cls = oracle.BalanceParams or capi.BalanceParams (the two
+    have the members of qlamd_balance_params)."""
+    import ctypes
+    p = cls()
+    for name in ROBOT_PARAM_FIELDS:
+        v = np.asarray(rp[name][i], dtype=np.float64)
+        if v.ndim == 0:
+            setattr(p, name, float(v))
+        elif v.ndim == 1:
+            setattr(p, name, (ctypes.c_double * v.size)(*v.tolist()))
+        else:
+            dst = getattr(p, name)
+            for a in range(v.shape[0]):
+                for b in range(v.shape[1]):
+                    dst[a][b] = float(v[a, b])
+    return p
