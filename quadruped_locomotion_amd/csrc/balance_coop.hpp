@@ -120,13 +120,51 @@ constexpr int kCoopNrmDoubles = 12 * 64; // 5 row kinds + parked Jacobian row (3
 constexpr int kRpKpT = 0, kRpKdT = 3, kRpKffT = 6, kRpKpR = 9, kRpKdR = 12, kRpKffR = 15, kRpS = 18, kRpWreg = 24, kRpMu = 25,
               kRpFmin = 26, kRpTauMax = 27, kRpFgScale = 28, kRpTgArm = 29;
 static_assert(kRpTgArm + 3 == QLAMD_ROBOT_PARAMS_DOUBLES, "the record ends with the gravity torque arm");
-template <bool kPerLeg, int kBlock = 64, bool kWarm = false, bool kParkInputs = false, bool kThroughput = false, bool kSmallForm = true,
-          bool kTable = false, bool kRobotParams = false>
+// The form of coop_robot a call site asks for, by name: CoopForm<WarmStart<true>, FromTable<true>> is the defaults below with
+// those two set -- each setter derives from what is there and hides one member.
+struct CoopDefaults {
+  static constexpr bool kPerLeg = false;     // per-leg surface normals from the caller
+  static constexpr int kBlock = 64;          // lanes of the workgroup (they share the staging of the model table)
+  static constexpr bool kWarm = false, kParkInputs = false, kThroughput = false, kSmallForm = true, kTable = false, kRobotParams = false;
+};
+template <class Base, class... Set> struct CoopFormOf { using type = Base; };
+template <class Base, class S, class... Rest>
+struct CoopFormOf<Base, S, Rest...> { using type = typename CoopFormOf<typename S::template on<Base>, Rest...>::type; };
+template <class... Set> using CoopForm = typename CoopFormOf<CoopDefaults, Set...>::type;
+template <bool v> struct PerLegNormals { template <class B> struct on : B { static constexpr bool kPerLeg = v; }; };
+template <int n> struct BlockLanes { template <class B> struct on : B { static constexpr int kBlock = n; }; };
+template <bool v> struct WarmStart { template <class B> struct on : B { static constexpr bool kWarm = v; }; };
+template <bool v> struct ParkInputs { template <class B> struct on : B { static constexpr bool kParkInputs = v; }; };
+template <bool v> struct ThroughputForm { template <class B> struct on : B { static constexpr bool kThroughput = v; }; };
+template <bool v> struct SmallForm { template <class B> struct on : B { static constexpr bool kSmallForm = v; }; };
+template <bool v> struct FromTable { template <class B> struct on : B { static constexpr bool kTable = v; }; };
+template <bool v> struct RobotParams { template <class B> struct on : B { static constexpr bool kRobotParams = v; }; };
+
+// Robot index of slot `slot` of a launch (row slot % 4 of wavefront slot / 4), as placed_index (context.hpp): live = the slot
+// holds a robot (an order entry outside [0, B) leaves it empty); an empty slot computes on robot B - 1 and writes nothing.
+// order: the placement's robot_order or NULL (the batch order).  (balance_coop_body.hpp and cold_retry_body keep the same
+// statements written out: through this function their kernels come out with other instructions -- profiles/r11/refactor_checks.md)
+__device__ __forceinline__ int64_t slot_robot(int64_t slot, int64_t B, const int32_t *order, bool &live) {
+  int64_t i = slot;
+  live = i < B;
+  if (!live) i = B - 1;
+  if (order) {
+    const int64_t o = order[i];
+    live = live && o >= 0 && o < B;
+    i = live ? o : B - 1;
+  }
+  return i;
+}
+
+template <class Form>
 __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs &s, int64_t irobot, bool robot_live_in,
                                            double *lds_tab, double *lds_row, double *lds_nrm,
                                            double *__restrict__ tau_out,
                                            double *__restrict__ grf_out, int32_t *__restrict__ status_out, bool cold = false,
                                            const double *__restrict__ robot_params = nullptr, double *lds_rp = nullptr) {
+  constexpr bool kPerLeg = Form::kPerLeg, kWarm = Form::kWarm, kParkInputs = Form::kParkInputs, kThroughput = Form::kThroughput,
+                 kSmallForm = Form::kSmallForm, kTable = Form::kTable, kRobotParams = Form::kRobotParams;
+  constexpr int kBlock = Form::kBlock;
   bool robot_live = robot_live_in;
   // a controller parameter: the robot's own (entry k of its staged record) or the context's
   const auto prm = [&](int k, const double &of_context) -> double {
@@ -200,9 +238,7 @@ __device__ __forceinline__ bool coop_robot(const DeviceParams &P, const CoopPtrs
   if (kPerLeg) { nWl[0] = s.normals[12 * i_in + 3 * leg]; nWl[1] = s.normals[12 * i_in + 3 * leg + 1]; nWl[2] = s.normals[12 * i_in + 3 * leg + 2]; }
   // (all loads above are in flight before the first of them is consumed)
   robot_live = robot_live && alive != 0;
-  const unsigned stance = robot_live ? (((sm & 0xFFu) ? 1u : 0u) | ((sm & 0xFF00u) ? 2u : 0u) |
-                                        ((sm & 0xFF0000u) ? 4u : 0u) | ((sm & 0xFF000000u) ? 8u : 0u))
-                                     : 0u;
+  const unsigned stance = robot_live ? support_mask(sm) : 0u;
   const int nS = __popc(stance);
   if constexpr (kTable) {
     const unsigned slot = QLAMD_SET_MEMORY_SLOT(stance);

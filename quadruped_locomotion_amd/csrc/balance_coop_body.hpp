@@ -23,6 +23,7 @@
       __builtin_amdgcn_s_setprio(3);
     }
   }
+  // (the slot's robot: coop::slot_robot's statements with the next order's write between them, written out -- see there)
   int64_t i = (int64_t)block * (4 * kCoopWaves) + row;
   bool live = i < B;
   if (!live) i = B - 1;
@@ -36,10 +37,20 @@
       i = live ? o : B - 1;
     }
   }
-  const coop::CoopPtrs cp{s.q, s.pos, s.quat, s.linvel, s.angvel, s.dpos, s.dquat, s.dlinvel, s.dangvel, s.stance,
-                          s.normals, s.wrench, s.live, s.support_only, kPlaced ? s.iterations : nullptr,
-                          kWarm ? s.prev_working_set : nullptr, kWarm ? s.working_set : nullptr, kWarm ? s.warm_retries : nullptr,
-                          s.record_doubles, kTable ? s.set_memory : nullptr};
+  // (coop_ptrs' fold by name, written out: as a call on the kernel's own parameter the placed kernels come out differently)
+  coop::CoopPtrs cp{};
+  cp.q = s.q; cp.pos = s.pos; cp.quat = s.quat; cp.linvel = s.linvel; cp.angvel = s.angvel;
+  cp.dpos = s.dpos; cp.dquat = s.dquat; cp.dlinvel = s.dlinvel; cp.dangvel = s.dangvel;
+  cp.stance = s.stance; cp.normals = s.normals;
+  cp.wrench = s.wrench; cp.live = s.live; cp.support_only = s.support_only;
+  if constexpr (kPlaced) cp.iterations = s.iterations;
+  if constexpr (kWarm) { cp.prev_working_set = s.prev_working_set; cp.working_set = s.working_set; cp.warm_retries = s.warm_retries; }
+  cp.record_doubles = s.record_doubles;
+  if constexpr (kTable) cp.set_memory = s.set_memory;
+  // the form: a placed launch carries the 6-variable form of the QP; the 168-register form (kMinWaves 3) installs a warm start's
+  // rows one after the other and, solving cold and placed, parks its inputs in LDS
+  using Form = coop::CoopForm<coop::PerLegNormals<kPerLeg>, coop::BlockLanes<64 * kCoopWaves>, coop::WarmStart<kWarm>, coop::FromTable<kTable>,
+                              coop::SmallForm<kPlaced>, coop::ThroughputForm<kMinWaves == 3>, coop::ParkInputs<kMinWaves == 3 && !kWarm && kPlaced>>;
 #ifdef QLAMD_STAMPS
 #pragma unroll 1
   for (int rep = 0; rep < 2; rep++) // second pass runs with a warm instruction cache
@@ -47,7 +58,7 @@
   // (inputs parked in LDS across the first form of the QP: the 168-register form solving cold -- no scratch then, 1-2 % on 65 536
   // to a million robots; the warm-started kernel is 3 % faster with them in registers and 20 bytes of scratch around the loop)
   {
-    const bool rejected = coop::coop_robot<kPerLeg, 64 * kCoopWaves, kWarm, kMinWaves == 3 && !kWarm && kPlaced, kMinWaves == 3, kPlaced, kTable>(
+    const bool rejected = coop::coop_robot<Form>(
         P, cp, i, live, tab, rows + row * coop::kCoopLdsDoubles, nrm + wave * coop::kCoopNrmDoubles, tau, grf, status);
     QL_BLOCK_STAMP(3);
     if constexpr (kWarm) {

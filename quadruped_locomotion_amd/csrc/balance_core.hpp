@@ -82,6 +82,14 @@ struct RobotIn {
   bool has_wrench;  // true: use `wrench` (computeForceDistribution's arguments) instead of the VMC
   double wrench[6]; // (F_B, T_B)
 };
+// The support flags of a robot ([4] bytes, any non-zero byte = the leg supports) read as ONE 32-bit word: the mask (bit l = leg l
+// supports) and the number of support legs.  Every kernel that reads the flags decodes them here.
+QL_HD unsigned support_mask(uint32_t w) {
+  return ((w & 0xFFu) ? 1u : 0u) | ((w & 0xFF00u) ? 2u : 0u) | ((w & 0xFF0000u) ? 4u : 0u) | ((w & 0xFF000000u) ? 8u : 0u);
+}
+QL_HD int support_legs(uint32_t w) {
+  return ((w & 0xFFu) ? 1 : 0) + ((w & 0xFF00u) ? 1 : 0) + ((w & 0xFF0000u) ? 1 : 0) + ((w & 0xFF000000u) ? 1 : 0);
+}
 
 // 1/x and 1/sqrt(x).  Device: hardware seed + two Newton steps (1-2 ulp, ~6 instructions) instead of the ~12-25
 // instruction IEEE division / square root sequences; host build (tests): the plain expressions.

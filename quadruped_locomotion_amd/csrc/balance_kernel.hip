@@ -3,6 +3,8 @@
 #include "balance_coop.hpp"
 #include "params_build.hpp"
 #include "context.hpp"
+#include "launch_form.hpp"
+#include "placement.hpp" // the placement sort: its kernels, the shadow wavefronts of a placed launch, its launches and entry
 
 #include <type_traits>
 
@@ -21,7 +23,7 @@ struct StatePtrs {
                         // others, runs beside this kernel on another stream)
   const int32_t *order; // [B] or NULL: slot s of the launch (row s % 4 of wavefront s / 4) takes robot order[s]
   int32_t *iterations;  // [B] or NULL: outer iterations of each robot's QP
-  // the placement of the NEXT launch, made by extra wavefronts in the shadow of this one (placement_wave below)
+  // the placement of the NEXT launch, made by extra wavefronts in the shadow of this one (placement_wave, placement.hpp)
   const int32_t *prev_iterations; // [B]: the counts it is made from (the previous launch's `iterations`)
   int32_t *next_order;            // [B] or NULL: where it goes.  With shadow_blocks == 0: QLAMD_PLACEMENT_NONE -- every slot writes its own
                                   // index here (no field of its own: one more pointer in the arguments cost the 168-register form 1 % at 65 536 robots)
@@ -63,13 +65,29 @@ __device__ __forceinline__ void load_robot(const StatePtrs &s, int64_t i, RobotI
     in.dangvel[k] = s.dangvel[3 * i + k];
   }
   const uint32_t m = *reinterpret_cast<const uint32_t *>(s.stance + 4 * i);
-  in.stance = ((m & 0xFFu) ? 1u : 0u) | ((m & 0xFF00u) ? 2u : 0u) | ((m & 0xFF0000u) ? 4u : 0u) |
-              ((m & 0xFF000000u) ? 8u : 0u);
+  in.stance = support_mask(m);
   in.has_wrench = s.wrench != nullptr;
   if (in.has_wrench) {
 #pragma unroll
     for (int k = 0; k < 6; k++) in.wrench[k] = s.wrench[6 * i + k];
   }
+}
+
+// StatePtrs -> what coop_robot takes, by the pointer groups the caller uses (the others stay NULL / 0): the iteration counts; the
+// warm start's sets and counter; the table; what only the context-wide entries and the whole tick have (an external wrench, the
+// live flags, support_only, the record layout).  In the order of CoopPtrs' members: the order the kernels fetch them in.
+enum : unsigned { kUseIterations = 1u, kUseWarm = 2u, kUseTable = 4u, kUseWrenchLive = 8u };
+template <unsigned kUse>
+__device__ __forceinline__ coop::CoopPtrs coop_ptrs(const StatePtrs &s) {
+  coop::CoopPtrs c{};
+  c.q = s.q; c.pos = s.pos; c.quat = s.quat; c.linvel = s.linvel; c.angvel = s.angvel;
+  c.dpos = s.dpos; c.dquat = s.dquat; c.dlinvel = s.dlinvel; c.dangvel = s.dangvel; c.stance = s.stance; c.normals = s.normals;
+  if constexpr (kUse & kUseWrenchLive) { c.wrench = s.wrench; c.live = s.live; c.support_only = s.support_only; }
+  if constexpr (kUse & kUseIterations) c.iterations = s.iterations;
+  if constexpr (kUse & kUseWarm) { c.prev_working_set = s.prev_working_set; c.working_set = s.working_set; c.warm_retries = s.warm_retries; }
+  if constexpr (kUse & kUseWrenchLive) c.record_doubles = s.record_doubles;
+  if constexpr (kUse & kUseTable) c.set_memory = s.set_memory;
+  return c;
 }
 
 // One wavefront per workgroup, RPW robots per wavefront (64, 16 or 4).  A small batch is spread
@@ -152,322 +170,6 @@ __global__ __launch_bounds__(64) void balance_step_kernel(const DeviceParams *__
   }
 }
 
-// Placement of the robots into the slots of the next launch from the iteration counts of the last one
-// (qlamd_placement_from_iterations): a stable counting sort by iteration count, hardest first (ties by robot index), then
-// the slot of each rank by policy:
-//   throughput  slot = rank: four neighbours of the sorted list share a wavefront.  The union of four similar add / drop
-//               sequences is the shortest there is, which is what counts once every SIMD holds several wavefronts, and the
-//               long wavefronts start first.
-//   latency     the hardest quarter one per wavefront (row 0 of wavefront r = rank r), each joined by the three easiest
-//               robots still to be had (rank B-1-e sits in row 1 + e % 3 of wavefront e / 3): a launch of one wavefront
-//               per SIMD lasts as long as its slowest wavefront, and next to three robots that finish early a hard robot
-//               runs at the speed it has alone (finished rows ride along as ghost rows, force_qp_coop.hpp).
-// It sits between two control steps of a caller that wants the hint used at once, so it is built for latency: one
-// workgroup of 1024 lanes takes 1024 G consecutive robots, robot g * 1024 + lane in its round g.  A robot's ordinal among
-// the robots of its wavefront and round with the same count is the return value of ONE LDS atomic on the counter
-// [bin][round][wavefront] (the lanes of one instruction that meet on an address are served in lane order); an exclusive
-// scan over the 512 G counters in (bin, round, wavefront) order turns them into first ranks; rank -> slot -> one store.
-// Batches beyond 4096 robots take several workgroups, which need the counts of the other workgroups per bin: a first
-// launch (placement_hist_kernel) leaves them in the context's scratch.
-constexpr int kPlaceThreads = 1024, kPlaceWaves = kPlaceThreads / 64, kPlaceBins = 24, kPlaceRounds = 4;
-__device__ __forceinline__ int place_bin(int v) { // bin 0 = hardest (the clamp compiles to one v_med3_i32)
-  const int h = v < 0 ? 0 : (v >= kPlaceBins ? kPlaceBins - 1 : v);
-  return kPlaceBins - 1 - h;
-}
-// The launches of their own also know a robot's CLASS when the caller's support flags are at hand (`support`: [B][4] bytes
-// read as one word per robot; NULL: one class): robots on more than two legs first, then the robots on at most two --
-// whose wavefronts then take the 6-variable form of the QP (balance_coop.hpp, "support legs first": a wavefront takes it
-// only when all four of its robots can).  Key = class * kPlaceBins + bin; sorted placement only (placing the hardest
-// robots one per wavefront mixes the classes by design).
-constexpr int kPlaceKeys = 2 * kPlaceBins;
-__device__ __forceinline__ int place_key(int v, const uint32_t *__restrict__ support, int64_t i) {
-  int key = place_bin(v);
-  if (support) {
-    const uint32_t w = support[i];
-    const int n = ((w & 0xFFu) ? 1 : 0) + ((w & 0xFF00u) ? 1 : 0) + ((w & 0xFF0000u) ? 1 : 0) + ((w & 0xFF000000u) ? 1 : 0);
-    key += n <= 2 ? kPlaceBins : 0;
-  }
-  return key;
-}
-__global__ __launch_bounds__(kPlaceThreads) void placement_hist_kernel(const int32_t *__restrict__ iters, int64_t B, int64_t per_block,
-                                                                      const uint32_t *__restrict__ support,
-                                                                      uint32_t *__restrict__ blockhist) {
-  __shared__ uint32_t h[kPlaceKeys];
-  if (threadIdx.x < kPlaceKeys) h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t lo = (int64_t)blockIdx.x * per_block, hi = lo + per_block < B ? lo + per_block : B;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += kPlaceThreads) atomicAdd(&h[place_key(iters[i], support, i)], 1u);
-  __syncthreads();
-  if (threadIdx.x < kPlaceKeys) blockhist[(int64_t)blockIdx.x * kPlaceKeys + threadIdx.x] = h[threadIdx.x];
-}
-template <int G>
-__global__ __launch_bounds__(kPlaceThreads) void placement_kernel(const int32_t *__restrict__ iters, int64_t B, int throughput,
-                                                                 const uint32_t *__restrict__ support,
-                                                                 const uint32_t *__restrict__ blockhist, int32_t *__restrict__ order) {
-  constexpr int kN = kPlaceKeys * G * kPlaceWaves, kPer = (kN + kPlaceThreads - 1) / kPlaceThreads; // counters, counters per lane in the scan
-  __shared__ uint32_t cnt[kN];
-  __shared__ uint32_t wtot[kPlaceWaves];
-  __shared__ uint32_t bin_base[kPlaceKeys];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t first = (int64_t)blockIdx.x * (kPlaceThreads * G);
-  int v[G];
-#pragma unroll
-  for (int g = 0; g < G; g++) { // all loads in flight before the first atomic
-    const int64_t i = first + g * kPlaceThreads + t;
-    v[g] = i < B ? place_key(iters[i], support, i) : -1;
-  }
-#pragma unroll
-  for (int k = 0; k < kPer; k++)
-    if (t + k * kPlaceThreads < kN) cnt[t + k * kPlaceThreads] = 0;
-  __shared__ uint32_t tot[kPlaceKeys], before[kPlaceKeys];
-  if (gridDim.x > 1) {
-    // several workgroups: robots of the harder bins anywhere, and of my bin in the workgroups before mine
-    if (t < kPlaceKeys) { tot[t] = 0; before[t] = 0; }
-    __syncthreads();
-    for (unsigned e = t; e < gridDim.x * kPlaceKeys; e += kPlaceThreads) {
-      const unsigned blk = e / kPlaceKeys, b = e - blk * kPlaceKeys;
-      const uint32_t c = blockhist[e];
-      atomicAdd(&tot[b], c);
-      if (blk < blockIdx.x) atomicAdd(&before[b], c);
-    }
-    __syncthreads();
-    if (t < kPlaceKeys) {
-      uint32_t harder = 0;
-      for (int b = 0; b < kPlaceKeys; b++) harder += b < t ? tot[b] : 0u;
-      bin_base[t] = harder + before[t];
-    }
-  }
-  __syncthreads();
-  uint32_t ord[G];
-#pragma unroll
-  for (int g = 0; g < G; g++) ord[g] = v[g] >= 0 ? atomicAdd(&cnt[(v[g] * G + g) * kPlaceWaves + wave], 1u) : 0u;
-  __syncthreads();
-  // exclusive scan of the counters in place: kPer consecutive counters per lane, then lanes, then wavefronts
-  uint32_t c[kPer], mine = 0;
-#pragma unroll
-  for (int k = 0; k < kPer; k++) { c[k] = t * kPer + k < kN ? cnt[t * kPer + k] : 0u; mine += c[k]; }
-  uint32_t incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(incl, d, 64);
-    incl += lane >= d ? o : 0u;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  uint32_t run = incl - mine;
-#pragma unroll
-  for (int w = 0; w < kPlaceWaves; w++) run += w < wave ? wtot[w] : 0u;
-#pragma unroll
-  for (int k = 0; k < kPer; k++) {
-    if (t * kPer + k < kN) cnt[t * kPer + k] = run;
-    run += c[k];
-  }
-  __syncthreads();
-  const int64_t W = (B + 3) / 4;
-#pragma unroll
-  for (int g = 0; g < G; g++) {
-    if (v[g] < 0) continue;
-    int64_t r = cnt[(v[g] * G + g) * kPlaceWaves + wave] + ord[g];
-    if (gridDim.x > 1) r += (int64_t)bin_base[v[g]] - cnt[v[g] * G * kPlaceWaves]; // my workgroup's harder bins come off
-    int64_t slot = r;
-    if (!throughput) {
-      const int64_t e = B - 1 - r;
-      slot = r < W ? 4 * r : 4 * (e / 3) + 1 + e % 3;
-    }
-    order[slot] = (int32_t)(first + g * kPlaceThreads + t);
-  }
-}
-
-// The same placement inside a placed launch, for the extra workgroups it carries when the caller asks for the next launch's
-// placement (qlamd_placement::next_robot_order): they run in the shadow of the solve -- a launch of a few thousand robots
-// lasts 9-24 us, one of these wavefronts a few us for its 1024 robots -- instead of as launches of their own between two
-// control steps (6-9 us).  One wavefront (= workgroup) per `chunk` robots, the first workgroups of the grid:
-// rounds of 64 robots; counters [key][round] in the workgroup's LDS (the solve's 13.5 KB).  Pass 1 counts (LDS atomics
-// without a return value), an exclusive scan in (key, round) order turns the counters into first ranks within the chunk,
-// pass 2 takes each robot's rank as the return value of one more atomic on its counter (lanes that meet on a counter are
-// served in lane order: rank order = index order within a key).  With several chunks a wavefront needs the others' counts
-// per key between the scan and pass 2: each leaves its own in the context's scratch and they meet at a barrier in global
-// memory (arrivals + generation, agent scope; the workgroups in front of a grid are dispatched first and all at once, so
-// they can wait for each other; the barrier resets itself, so a hipGraph can replay the launch).  Keys: the iteration
-// count's bin, and with a sorted placement also the robot's class (place_key: robots on more than two legs first).
-// A lone wavefront issues one instruction per ~5.5 cycles and waits out every memory round trip, so the loop bodies are
-// counted in instructions (32-bit index arithmetic, the division by 3 as a multiplication, one clamp per count),
-// kShadowChunk rounds have their loads in flight together, and the last, ragged rounds are the only ones that check
-// indices.  Measured and dropped (profiles/r5/placed_probe.txt): ONE atomic pass whose return values are kept until the
-// scan is done -- in registers (13 000 instructions of unrolled code), as bytes in LDS (16 us at 4096 robots: sub-word LDS
-// stores) or as words of four rounds (14.6 us, and 16 KB of LDS per workgroup cost every placed launch 0.3 us).
-constexpr int kShadowLdsBytes = (4 * kTabPerLeg + 4 * coop::kCoopLdsDoubles + coop::kCoopNrmDoubles) * 8;
-// robots per shadow wavefront.  Below the throughput form's batches: 1024 with a warm start (4096 robots: 4 wavefronts, 6 us
-// -- shorter than the shortest solve, a warm-started calm batch's 9.5 us), 2048 without (8 us against the 13.4 us of a calm
-// batch solved cold: every shadow wavefront shares a SIMD with a wavefront that solves, and two of them cost the placed
-// loop of 4096 robots 0.3 us less than four: profiles/r5/ab_shadow_blocks.txt).  4096 from there (65 536 robots: 16
-// wavefronts, 13 us of a 70 us launch; with 64 of them every one reads 64 x 48 counts and the launch is 3-5 us longer).
-constexpr int kShadowChunkWarm = 1024, kShadowChunkCold = 2048, kShadowChunkLarge = 4096, kShadowMaxBlocks = 256;
-static_assert((kShadowChunkLarge / 64) * kPlaceKeys * 4 + kPlaceKeys * 4 <= kShadowLdsBytes, "the shadow wavefront's counters live in the solve's LDS");
-constexpr int kShadowChunk = 16; // rounds whose loads are in flight together: a chunk's 1024 robots
-typedef __attribute__((address_space(3))) uint32_t lds_u32; // (a generic pointer would turn the atomics into flat ones)
-template <bool kThroughput>
-__device__ __forceinline__ uint32_t place_slot(uint32_t rk, uint32_t B, uint32_t W) {
-  if constexpr (kThroughput) return rk;
-  const uint32_t e = B - 1u - rk, q = __umulhi(e, 0xAAAAAAABu) >> 1; // e / 3
-  return rk < W ? 4u * rk : 4u * q + 1u + (e - 3u * q);
-}
-// sidx of S: my chunk; support: the robots' support flags when the keys carry the class (sorted placement), else NULL
-__device__ __forceinline__ void placement_wave(const int32_t *__restrict__ iters, int64_t B64, int throughput,
-                                               int32_t *__restrict__ order, lds_u32 *cnt, uint32_t sidx, uint32_t S,
-                                               uint32_t chunk, const uint32_t *__restrict__ support, uint32_t *__restrict__ ghist,
-                                               uint32_t *__restrict__ gsync, uint32_t max_polls) {
-  const uint32_t lane = threadIdx.x & 63u, B = (uint32_t)B64, W = (B + 3u) >> 2;
-  const uint32_t lo = sidx * chunk;
-  const uint32_t n = lo >= B ? 0u : (B - lo < chunk ? B - lo : chunk); // my robots
-  const uint32_t R = (n + 63u) >> 6, full = n >> 6;      // rounds, rounds without a missing robot
-  const bool classes = throughput && support != nullptr;
-  const uint32_t nkeys = classes ? kPlaceKeys : kPlaceBins, N = nkeys * R; // counters
-  lds_u32 *adj = cnt + N;                                // what turns a rank within the chunk into the rank of the batch, per key
-  for (uint32_t k = lane; k < N + nkeys; k += 64) cnt[k] = 0;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  const auto run = [&](auto Classes, auto Thr) {
-    constexpr bool kClasses = decltype(Classes)::value, kThr = decltype(Thr)::value;
-    const auto key_of = [&](int v, uint32_t w) -> uint32_t {
-      uint32_t key = (uint32_t)place_bin(v);
-      if constexpr (kClasses) {
-        const int legs = ((w & 0xFFu) ? 1 : 0) + ((w & 0xFF00u) ? 1 : 0) + ((w & 0xFF0000u) ? 1 : 0) + ((w & 0xFF000000u) ? 1 : 0);
-        key += legs <= 2 ? (uint32_t)kPlaceBins : 0u;
-      }
-      return key;
-    };
-    // one pass over my robots: kPass 1 counts, kPass 2 ranks and stores
-    const auto pass = [&](auto Pass) {
-      constexpr int kPass = decltype(Pass)::value;
-      for (uint32_t r0 = 0; r0 < R; r0 += kShadowChunk) {
-        if (r0 + kShadowChunk <= full) {
-          int v[kShadowChunk];
-          uint32_t w[kShadowChunk], rk[kShadowChunk];
-#pragma unroll
-          for (int k = 0; k < kShadowChunk; k++) {
-            v[k] = iters[lo + (r0 + k) * 64u + lane];
-            w[k] = kClasses ? support[lo + (r0 + k) * 64u + lane] : 0u;
-          }
-#pragma unroll
-          for (int k = 0; k < kShadowChunk; k++) {
-            const uint32_t key = key_of(v[k], w[k]);
-            w[k] = key;
-            lds_u32 *c = cnt + key * R + (r0 + k);
-            if constexpr (kPass == 1) (void)__hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else rk[k] = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          }
-          if constexpr (kPass == 2) {
-#pragma unroll
-            for (int k = 0; k < kShadowChunk; k++)
-              order[place_slot<kThr>(rk[k] + adj[w[k]], B, W)] = (int32_t)(lo + (r0 + k) * 64u + lane);
-          }
-        } else {
-          for (uint32_t r = r0; r < R && r < r0 + kShadowChunk; r++) {
-            const uint32_t i = r * 64u + lane;
-            if (i < n) {
-              const uint32_t key = key_of(iters[lo + i], kClasses ? support[lo + i] : 0u);
-              lds_u32 *c = cnt + key * R + r;
-              if constexpr (kPass == 1) (void)__hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              else {
-                const uint32_t rk = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                order[place_slot<kThr>(rk + adj[key], B, W)] = (int32_t)(lo + i);
-              }
-            }
-          }
-        }
-      }
-    };
-    pass(std::integral_constant<int, 1>{});
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // ---- exclusive scan in (key, round) order: `per` consecutive counters per lane
-    {
-      const uint32_t per = (N + 63u) >> 6, k0 = lane * per, k1 = k0 + per < N ? k0 + per : N;
-      uint32_t mine = 0;
-      for (uint32_t k = k0; k < k1; k++) mine += cnt[k];
-      uint32_t incl = mine;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        incl += lane >= (uint32_t)d ? o : 0u;
-      }
-      uint32_t running = incl - mine;
-      for (uint32_t k = k0; k < k1; k++) { const uint32_t c = cnt[k]; cnt[k] = running; running += c; }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (S > 1) {
-      // ---- the other chunks: lane k < nkeys owns key k.  My count of it goes to the scratch, the barrier, then
-      //      rank of the batch = robots of harder keys anywhere + robots of my key in the chunks before mine + rank in my chunk
-      const uint32_t start = (lane < nkeys && R > 0) ? cnt[lane * R] : 0u;
-      const uint32_t next = (lane + 1u < nkeys && R > 0) ? cnt[(lane + 1u) * R] : n;
-      if (lane < nkeys) __hip_atomic_store(ghist + sidx * kPlaceKeys + lane, R > 0 ? next - start : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      // The barrier: arrivals in gsync[0], its state in gsync[1].  A launch finds the state at an even value g and leaves it at
-      // g + 2 (everybody arrived: the last one says so) or at g + 4 (somebody gave up waiting -- g + 1, odd -- and the last one
-      // to arrive closed the launch).  Both transitions away from g are compare-and-swaps, so a launch has ONE outcome, and
-      // every wavefront can tell which whenever it looks (odd: given up; g + 2: complete; g + 4: given up and closed).  The
-      // waiting is bounded (a second or two: a device shared with something that keeps these wavefronts from running together
-      // must not hang), and a launch that gives up writes the identity order -- a valid placement, which costs the next launch
-      // time, never a result.
-      int gave_up = 0;
-      if (lane == 0) {
-        const uint32_t g = __hip_atomic_load(gsync + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t arrived = __hip_atomic_fetch_add(gsync, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = arrived == S - 1u;
-        if (last) __hip_atomic_store(gsync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g & 1u) { // somebody gave up before I got here
-          gave_up = 1;
-          if (last) __hip_atomic_store(gsync + 1, g + 3u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (last) {
-          uint32_t now = g;
-          if (!__hip_atomic_compare_exchange_strong(gsync + 1, &now, g + 2u, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {
-            __hip_atomic_store(gsync + 1, g + 4u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            gave_up = 1;
-          }
-        } else {
-          uint32_t now = g;
-          for (unsigned spin = 0;; spin++) {
-            now = __hip_atomic_load(gsync + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            if (now != g) break;
-            if (spin >= max_polls) {
-              if (__hip_atomic_compare_exchange_strong(gsync + 1, &now, g + 1u, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) now = g + 1u;
-              break; // (lost the exchange: `now` holds what the winner wrote)
-            }
-            __builtin_amdgcn_s_sleep(4);
-          }
-          gave_up = now != g + 2u ? 1 : 0;
-        }
-      }
-      gave_up = __builtin_amdgcn_readfirstlane(gave_up);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      if (gave_up) {
-        for (uint32_t i = lane; i < n; i += 64) order[lo + i] = (int32_t)(lo + i);
-        if (sidx == 0 && lane == 0) atomicAdd(gsync + kSyncGiveUps, 1u); // one count per launch (QLAMD_COUNTER_PLACEMENT_GIVE_UPS)
-        return;
-      }
-      uint32_t total = 0, before = 0;
-      if (lane < nkeys) {
-        for (uint32_t b = 0; b < S; b++) {
-          const uint32_t h = __hip_atomic_load(ghist + b * kPlaceKeys + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          total += h;
-          before += b < sidx ? h : 0u;
-        }
-      }
-      uint32_t incl = total;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        incl += lane >= (uint32_t)d ? o : 0u;
-      }
-      if (lane < nkeys) adj[lane] = (incl - total) + before - start;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    }
-    pass(std::integral_constant<int, 2>{});
-  };
-  if (classes) run(std::true_type{}, std::true_type{});
-  else if (throughput) run(std::false_type{}, std::true_type{});
-  else run(std::false_type{}, std::false_type{});
-}
-
 // The second attempt of the rows whose warm start was rejected (balance_coop_kernel<..., kWarm = true>, below): the plain kernel's
 // body as a function of its own that ENDS THE WAVEFRONT -- nothing of the caller's is live across the call -- and takes what it
 // needs from the kernel's argument segment again (coop::kernel_arguments_again: the caller passes the segment's address -- a
@@ -480,6 +182,7 @@ __device__ __forceinline__ void cold_retry_body(const BalanceCoopArgs *args, dou
   double *tab = lds, *rows = lds + 4 * kTabPerLeg, *nrm = rows + 4 * coop::kCoopLdsDoubles;
   const int row = threadIdx.x >> 4;
   const unsigned blk = blockIdx.x - (unsigned)a.s.shadow_blocks;
+  // (coop::slot_robot's statements, written out: see there)
   int64_t ir = (int64_t)blk * 4 + row;
   const bool inside = ir < a.B;
   if (!inside) ir = a.B - 1;
@@ -487,9 +190,9 @@ __device__ __forceinline__ void cold_retry_body(const BalanceCoopArgs *args, dou
     const int64_t o = a.s.order[ir];
     ir = (inside && o >= 0 && o < a.B) ? o : a.B - 1;
   }
-  const coop::CoopPtrs cold{a.s.q, a.s.pos, a.s.quat, a.s.linvel, a.s.angvel, a.s.dpos, a.s.dquat, a.s.dlinvel, a.s.dangvel, a.s.stance,
-                            a.s.normals, a.s.wrench, a.s.live, a.s.support_only, a.s.iterations, nullptr, nullptr, nullptr, a.s.record_doubles};
-  (void)coop::coop_robot<kPerLeg, 64, false, kMinWaves == 3>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.tau, a.grf, a.status);
+  const coop::CoopPtrs cold = coop_ptrs<kUseIterations | kUseWrenchLive>(a.s);
+  using Cold = coop::CoopForm<coop::PerLegNormals<kPerLeg>, coop::ParkInputs<kMinWaves == 3>>;
+  (void)coop::coop_robot<Cold>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.tau, a.grf, a.status);
   if (rejected && (threadIdx.x & 15) == 0 && a.s.working_set) a.s.working_set[ir] = 0u;
 }
 template <bool kPerLeg, int kMinWaves>
@@ -511,16 +214,7 @@ __device__ __attribute__((noinline, noreturn)) void balance_table_retry(const Ba
 // shared) costs 2.3 us at 4096 robots and 20 % at 65536 -- the barrier behind the table ties the start of four
 // wavefronts together and workgroups leave their compute unit only when their slowest wavefront has finished.
 constexpr int kCoopWaves = 1;
-#ifndef QLAMD_THROUGHPUT_BATCH
-#define QLAMD_THROUGHPUT_BATCH 16384 // robots from which the three-wavefront form of the balance kernel runs
-#endif
-#ifndef QLAMD_THREE_WAVE_WARM_BATCH
-// ... of the warm-started kernel: later, because its two-wavefront form installs by rounds and lets robots without a set build
-// one by rounds, which the 168 registers of the other form have no room for (trot, placed + warm loop, us per step, two- against
-// three-wavefront form: 16 384 robots 30.0 / 32.6, 20 480: 33.6 / 34.3, 24 576: 37.9 / 37.1, 32 768: 45.6 / 42.8, 65 536:
-// 76.7 / 70.5 -- profiles/r6/ab_three_wave_threshold.txt)
-#define QLAMD_THREE_WAVE_WARM_BATCH 22528
-#endif
+// (from which batch the three-wavefront form runs: QLAMD_THROUGHPUT_BATCH, QLAMD_THREE_WAVE_WARM_BATCH, launch_form.hpp)
 // kMinWaves wavefronts per SIMD at least: 2 (at most 256 registers: the large-batch throughput halves without it) for the
 // latency form, 3 (at most 168 registers; 12 wavefronts x 13 056 bytes of LDS fit a compute unit) for the throughput form
 // that large batches take (QLAMD_THROUGHPUT_BATCH): two wavefronts of dependent instruction streams cannot fill a SIMD's
@@ -579,20 +273,12 @@ __device__ __forceinline__ bool robot_params_rows(const DeviceParams &P, const S
                                                   int32_t *status, const double *robot_params, double *lds, bool cold, bool only) {
   double *tab = lds, *rows = lds + 4 * kTabPerLeg, *nrm = rows + 4 * coop::kCoopLdsDoubles, *rp = lds + kCoopLdsTotal;
   const int row = threadIdx.x >> 4;
-  int64_t i = (int64_t)blockIdx.x * 4 + row;
-  bool live = i < B;
-  if (!live) i = B - 1;
-  if (s.order) {
-    const int64_t o = s.order[i];
-    live = live && o >= 0 && o < B;
-    i = live ? o : B - 1;
-  }
-  const coop::CoopPtrs cp{s.q, s.pos, s.quat, s.linvel, s.angvel, s.dpos, s.dquat, s.dlinvel, s.dangvel, s.stance,
-                          s.normals, nullptr, nullptr, 0, s.iterations, kWarm ? s.prev_working_set : nullptr,
-                          kWarm ? s.working_set : nullptr, kWarm ? s.warm_retries : nullptr, 0, kTable ? s.set_memory : nullptr};
-  return coop::coop_robot<kPerLeg, 64, kWarm, false, false, true, kTable, true>(
-      P, cp, i, live && only, tab, rows + row * coop::kCoopLdsDoubles, nrm, tau, grf, status, cold, robot_params,
-      rp + row * QLAMD_ROBOT_PARAMS_DOUBLES);
+  bool live;
+  const int64_t i = coop::slot_robot((int64_t)blockIdx.x * 4 + row, B, s.order, live);
+  const coop::CoopPtrs cp = coop_ptrs<kUseIterations | (kWarm ? kUseWarm : 0u) | (kTable ? kUseTable : 0u)>(s);
+  using Form = coop::CoopForm<coop::PerLegNormals<kPerLeg>, coop::WarmStart<kWarm>, coop::FromTable<kTable>, coop::RobotParams<true>>;
+  return coop::coop_robot<Form>(P, cp, i, live && only, tab, rows + row * coop::kCoopLdsDoubles, nrm, tau, grf, status, cold, robot_params,
+                                rp + row * QLAMD_ROBOT_PARAMS_DOUBLES);
 }
 // the second attempt of its rejected rows (as balance_cold_retry: a function that ends the wavefront, one per calling kernel)
 template <bool kPerLeg, bool kTable>
@@ -690,28 +376,17 @@ __global__ __launch_bounds__(64) void leg_kinematics_kernel(const DeviceParams *
   if (grav) { grav[3 * t] = Gq[0]; grav[3 * t + 1] = Gq[1]; grav[3 * t + 2] = Gq[2]; }
 }
 
-
-
 template <int RPW>
 hipError_t launch_balance(const qlamd_context *ctx, const StatePtrs &s, int64_t B, double *tau, double *grf,
                           int32_t *status, hipStream_t st) {
   const size_t lds = ((size_t)RPW * kScratchDoubles + 4 * kTabPerLeg) * sizeof(double);
   const unsigned grid = (unsigned)((B + RPW - 1) / RPW);
-  if (s.normals) {
-    auto k = balance_step_kernel<RPW, true>;
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, ctx->d_params, s, B, tau, grf, status);
-  } else {
-    auto k = balance_step_kernel<RPW, false>;
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, ctx->d_params, s, B, tau, grf, status);
+  const auto k = s.normals ? balance_step_kernel<RPW, true> : balance_step_kernel<RPW, false>;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
   }
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, ctx->d_params, s, B, tau, grf, status);
   return hipGetLastError();
 }
 
@@ -723,7 +398,6 @@ void qlamd_balance_default_params(qlamd_balance_params *p) { if (p) default_bala
 void qlamd_default_robot_model(qlamd_robot_model *m) { if (m) default_robot_model(m); }
 int qlamd_version(void) { return QLAMD_VERSION_MAJOR * 1000 + QLAMD_VERSION_MINOR; }
 unsigned qlamd_set_memory_slot(unsigned support_mask) { return QLAMD_SET_MEMORY_SLOT(support_mask); }
-
 
 const char *qlamd_strerror(int code) {
   switch (code) {
@@ -750,36 +424,13 @@ int qlamd_context_create(const qlamd_balance_params *params, const qlamd_robot_m
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) return QLAMD_ERR_HIP;
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return QLAMD_ERR_NO_DEVICE;
-  qlamd_context *ctx = new (std::nothrow) qlamd_context;
+  qlamd_context *ctx = new (std::nothrow) qlamd_context(); // (value-initialised: every pointer NULL, every count and flag 0)
   if (!ctx) return QLAMD_ERR_OUT_OF_MEMORY;
   ctx->device = device;
-  ctx->rpw_override = 0;
   ctx->num_cu = prop.multiProcessorCount;
-  ctx->ws = nullptr;
-  ctx->ws_bytes = 0;
-  ctx->pinned = nullptr;
-  ctx->pinned_bytes = 0;
-  ctx->wire_tpl = nullptr;
-  ctx->wire_flip = 0;
-  ctx->tick_ws = nullptr;
-  ctx->tick_ws_bytes = 0;
-  ctx->place_ws = nullptr;
-  ctx->place_ws_bytes = 0;
-  ctx->place_sync = nullptr;
   ctx->placement_wait = 1u << 13;
-  ctx->has_next_placement = false;
-  ctx->tick_place_state = nullptr;
-  ctx->tick_place_batch = 0;
-  ctx->tick_place_count = 0;
   ctx->on_failure = QLAMD_ON_FAILURE_ZERO;
   ctx->dynamics_form = QLAMD_DYNAMICS_AUTO;
-  ctx->state_record_doubles = 0;
-  ctx->depth = 0;
-  ctx->last_stream = nullptr;
-  ctx->done_event = nullptr;
-  ctx->done_recorded = false;
-  ctx->had_work = false;
-  ctx->multi_stream = false;
   qlamd_robot_model m;
   if (model) m = *model; else default_robot_model(&m);
   build_device_params(*params, m, &ctx->params);
@@ -792,7 +443,6 @@ int qlamd_context_create(const qlamd_balance_params *params, const qlamd_robot_m
     ctx->base_I[3] = I[3] + bm * (cc - c[1] * c[1]); ctx->base_I[4] = I[4] - bm * c[1] * c[2];
     ctx->base_I[5] = I[5] + bm * (cc - c[2] * c[2]);
   }
-  ctx->d_params = nullptr;
   // (the placement scratch for batches up to 1 M robots comes with the context: 48 KB, and no placement call of a
   // sensible size ever has to allocate inside a stream capture)
   const size_t place_bytes = (size_t)256 * kPlaceKeys * sizeof(uint32_t);
@@ -884,80 +534,51 @@ int qlamd_get_counter(qlamd_context *ctx, int counter, int64_t *value) {
 } // extern "C"
 
 namespace {
-// qlamd_placement_from_iterations on device pointers (the caller holds the context's guard)
-// d_support: the robots' support flags ([B][4] bytes, device) or NULL -- the class of the sorted placement (place_key)
-int launch_placement(qlamd_context *ctx, const int32_t *d_it, int64_t batch, int throughput, int32_t *d_ord, hipStream_t st,
-                     const uint8_t *d_support = nullptr) {
-  const uint32_t *sup = throughput ? reinterpret_cast<const uint32_t *>(d_support) : nullptr;
-  if (batch <= kPlaceRounds * kPlaceThreads)
-    hipLaunchKernelGGL(placement_kernel<kPlaceRounds>, dim3(1), dim3(kPlaceThreads), 0, st, d_it, batch, throughput, sup, nullptr, d_ord);
-  else {
-    // several workgroups (the LDS atomics of one compute unit serve about one robot per cycle: 4096 robots per workgroup
-    // keep a launch at 3-4 us whatever the batch): their counts per bin go through the context's placement scratch
-    // (sized for 1 M robots when the context is created; growing it is an allocation, which a stream capture cannot take)
-    const int64_t per_block = (int64_t)kPlaceRounds * kPlaceThreads;
-    const unsigned nb = (unsigned)((batch + per_block - 1) / per_block);
-    const size_t need = (size_t)nb * kPlaceKeys * sizeof(uint32_t);
-    if (ctx->place_ws_bytes < need) {
-      if (CallGuard::capturing(st)) return QLAMD_ERR_NEEDS_RESERVE;
-      if (hipStreamSynchronize(st) != hipSuccess) return QLAMD_ERR_HIP;
-      if (ctx->place_ws) (void)hipFree(ctx->place_ws);
-      ctx->place_ws = nullptr;
-      ctx->place_ws_bytes = 0;
-      if (hipMalloc(&ctx->place_ws, need) != hipSuccess) return QLAMD_ERR_OUT_OF_MEMORY;
-      ctx->place_ws_bytes = need;
-    }
-    hipLaunchKernelGGL(placement_hist_kernel, dim3(nb), dim3(kPlaceThreads), 0, st, d_it, batch, per_block, sup, (uint32_t *)ctx->place_ws);
-    hipLaunchKernelGGL(placement_kernel<kPlaceRounds>, dim3(nb), dim3(kPlaceThreads), 0, st, d_it, batch, throughput, sup,
-                       (const uint32_t *)ctx->place_ws, d_ord);
-  }
-  return hipGetLastError() == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
-}
-bool throughput_policy(int policy, int64_t batch) {
-  return policy == QLAMD_PLACEMENT_THROUGHPUT || (policy == QLAMD_PLACEMENT_AUTO && batch >= QLAMD_THROUGHPUT_BATCH);
-}
-__global__ void identity_order_kernel(int32_t *order, int64_t B) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < B) order[i] = (int32_t)i;
-}
-} // namespace
-
-int qlamd::rt::placement_launch(qlamd_context *ctx, const int32_t *d_iterations, int64_t batch, int policy, int32_t *d_order,
-                                hipStream_t st, const uint8_t *d_support) {
-  if (policy == QLAMD_PLACEMENT_NONE) { // the batch order
-    hipLaunchKernelGGL(identity_order_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, d_order, batch);
-    return hipGetLastError() == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
-  }
-  return launch_placement(ctx, d_iterations, batch, throughput_policy(policy, batch) ? 1 : 0, d_order, st, d_support);
-}
-
-int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, int layout, const double *wrench, const uint8_t *live,
-                              int support_only, const qlamd_placement &pl, int64_t batch, double *d_tau, double *d_grf,
-                              int32_t *d_status, hipStream_t st) {
-  const bool table = pl.set_memory != nullptr; // (instead of prev_working_set: the entries have checked that)
-  const bool warm = pl.prev_working_set || pl.working_set || table;
-  // (prev_working_set == working_set is fine: a robot's set is read and written by its own 16 lanes only -- updated in place)
-  const bool placed = pl.robot_order || pl.iterations || pl.next_robot_order || warm;
-  const int policy = pl.next_robot_order ? effective_policy(pl.policy, batch, warm) : QLAMD_PLACEMENT_NONE;
+// The launch's StatePtrs from the caller's state and placement (arrays on the device); the context's counter of rejected warm
+// starts.  What only some launches have -- wrench, live flags, record layout, the shadow wavefronts -- is theirs to add.
+StatePtrs state_ptrs(const qlamd_context *ctx, const qlamd_state_batch &in, const qlamd_placement &pl) {
   StatePtrs s{};
   s.q = in.joint_position; s.pos = in.base_position; s.quat = in.base_orientation;
   s.linvel = in.base_linear_velocity; s.angvel = in.base_angular_velocity;
   s.dpos = in.desired_position; s.dquat = in.desired_orientation;
   s.dlinvel = in.desired_linear_velocity; s.dangvel = in.desired_angular_velocity;
   s.stance = in.support_leg; s.normals = in.surface_normal;
-  s.wrench = wrench; s.live = live; s.support_only = support_only;
   s.order = pl.robot_order; s.iterations = pl.iterations;
-  s.record_doubles = layout == QLAMD_STATE_RECORDS ? QLAMD_STATE_RECORD_DOUBLES : 0;
-  s.prev_working_set = pl.prev_working_set;
-  s.working_set = pl.working_set;
-  s.set_memory = pl.set_memory;
+  s.prev_working_set = pl.prev_working_set; s.working_set = pl.working_set; s.set_memory = pl.set_memory;
   s.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
+  return s;
+}
+// the kernel of a form (every instantiation of the two families has the one signature: the static_asserts behind them)
+using CoopKernel = decltype(&balance_coop_kernel<false, 2, true, true>);
+template <bool kPerLeg, int kMinWaves>
+CoopKernel coop_kernel_of(const LaunchForm &f) {
+  if (f.table) return balance_table_kernel<kPerLeg, kMinWaves>;
+  if (f.warm) return balance_coop_kernel<kPerLeg, kMinWaves, true, true>;
+  if (f.placed) return balance_coop_kernel<kPerLeg, kMinWaves, true>;
+  return balance_coop_kernel<kPerLeg, kMinWaves, false>;
+}
+CoopKernel coop_kernel_of(const LaunchForm &f) {
+  if (f.per_leg) return coop_kernel_of<true, 2>(f);
+  return f.waves == 3 ? coop_kernel_of<false, 3>(f) : coop_kernel_of<false, 2>(f);
+}
+} // namespace
+
+int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, int layout, const double *wrench, const uint8_t *live,
+                              int support_only, const qlamd_placement &pl, int64_t batch, double *d_tau, double *d_grf,
+                              int32_t *d_status, hipStream_t st) {
+  // (table: instead of prev_working_set, the entries have checked that; prev_working_set == working_set is fine: a robot's set is
+  // read and written by its own 16 lanes only -- updated in place)
+  const LaunchForm form = balance_launch_form(in.surface_normal != nullptr, batch, pl.prev_working_set || pl.working_set, pl.set_memory != nullptr,
+                                              pl.robot_order || pl.iterations || pl.next_robot_order);
+  const int policy = pl.next_robot_order ? effective_policy(pl.policy, batch, form.warm) : QLAMD_PLACEMENT_NONE;
+  StatePtrs s = state_ptrs(ctx, in, pl);
+  s.wrench = wrench; s.live = live; s.support_only = support_only;
+  s.record_doubles = layout == QLAMD_STATE_RECORDS ? QLAMD_STATE_RECORD_DOUBLES : 0;
   // the next launch's placement: by extra wavefronts in front of this launch
-  const int chunk = batch >= QLAMD_THROUGHPUT_BATCH ? kShadowChunkLarge : (warm ? kShadowChunkWarm : kShadowChunkCold);
+  const int chunk = batch >= QLAMD_THROUGHPUT_BATCH ? kShadowChunkLarge : (form.warm ? kShadowChunkWarm : kShadowChunkCold);
   const int64_t shadows = (batch + chunk - 1) / chunk;
-  const bool three_wave_form = !in.surface_normal && batch >= (warm ? QLAMD_THREE_WAVE_WARM_BATCH : QLAMD_THROUGHPUT_BATCH);
   if (pl.next_robot_order && policy == QLAMD_PLACEMENT_NONE) {
-    if (!three_wave_form) s.next_order = pl.next_robot_order; // (shadow_blocks stays 0: written by the slots themselves)
+    if (form.waves != 3) s.next_order = pl.next_robot_order; // (shadow_blocks stays 0: written by the slots themselves)
   } else if (pl.next_robot_order && shadows <= kShadowMaxBlocks && pick_rpw(ctx, batch) == 4) {
     s.prev_iterations = pl.prev_iterations;
     s.next_order = pl.next_robot_order;
@@ -973,25 +594,7 @@ int qlamd::rt::balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, i
   switch (pick_rpw(ctx, batch)) {
     case 4: {
       const unsigned grid = (unsigned)((batch + 4 * kCoopWaves - 1) / (4 * kCoopWaves)) + (unsigned)s.shadow_blocks;
-#define QL_LAUNCH_COOP(PERLEG, WAVES)                                                                                        \
-  do {                                                                                                                       \
-    if (table)                                                                                                               \
-      hipLaunchKernelGGL((balance_table_kernel<PERLEG, WAVES>), dim3(grid), dim3(64 * kCoopWaves), 0, st, ctx->d_params, s,  \
-                         batch, d_tau, d_grf, d_status);                                                                     \
-    else if (warm)                                                                                                           \
-      hipLaunchKernelGGL((balance_coop_kernel<PERLEG, WAVES, true, true>), dim3(grid), dim3(64 * kCoopWaves), 0, st,         \
-                         ctx->d_params, s, batch, d_tau, d_grf, d_status);                                                   \
-    else if (placed)                                                                                                         \
-      hipLaunchKernelGGL((balance_coop_kernel<PERLEG, WAVES, true>), dim3(grid), dim3(64 * kCoopWaves), 0, st, ctx->d_params, \
-                         s, batch, d_tau, d_grf, d_status);                                                                  \
-    else                                                                                                                     \
-      hipLaunchKernelGGL((balance_coop_kernel<PERLEG, WAVES, false>), dim3(grid), dim3(64 * kCoopWaves), 0, st,              \
-                         ctx->d_params, s, batch, d_tau, d_grf, d_status);                                                   \
-  } while (0)
-      if (s.normals) QL_LAUNCH_COOP(true, 2);
-      else if (batch >= (warm ? QLAMD_THREE_WAVE_WARM_BATCH : QLAMD_THROUGHPUT_BATCH)) QL_LAUNCH_COOP(false, 3);
-      else QL_LAUNCH_COOP(false, 2);
-#undef QL_LAUNCH_COOP
+      hipLaunchKernelGGL(coop_kernel_of(form), dim3(grid), dim3(64 * kCoopWaves), 0, st, ctx->d_params, s, batch, d_tau, d_grf, d_status);
       e = hipGetLastError();
       break;
     }
@@ -1013,33 +616,15 @@ int robot_params_launch(qlamd_context *ctx, const qlamd_state_batch &in, const q
                         int64_t batch, double *d_tau, double *d_grf, int32_t *d_status, hipStream_t st) {
   const bool table = pl.set_memory != nullptr;
   const bool warm = pl.prev_working_set || pl.working_set || table;
-  StatePtrs s{};
-  s.q = in.joint_position; s.pos = in.base_position; s.quat = in.base_orientation;
-  s.linvel = in.base_linear_velocity; s.angvel = in.base_angular_velocity;
-  s.dpos = in.desired_position; s.dquat = in.desired_orientation;
-  s.dlinvel = in.desired_linear_velocity; s.dangvel = in.desired_angular_velocity;
-  s.stance = in.support_leg; s.normals = in.surface_normal;
-  s.order = pl.robot_order; s.iterations = pl.iterations;
-  s.prev_working_set = pl.prev_working_set;
-  s.working_set = pl.working_set;
-  s.set_memory = pl.set_memory;
-  s.warm_retries = (uint32_t *)ctx->place_sync + kSyncWarmRetries;
+  const StatePtrs s = state_ptrs(ctx, in, pl);
   const unsigned grid = (unsigned)((batch + 3) / 4);
-#define QL_LAUNCH_ROBOT_PARAMS(PERLEG)                                                                                          \
-  do {                                                                                                                          \
-    if (table)                                                                                                                  \
-      hipLaunchKernelGGL((balance_robot_params_kernel<PERLEG, true, true>), dim3(grid), dim3(64), 0, st, ctx->d_params, s, batch, \
-                         d_tau, d_grf, d_status, d_robot_params);                                                               \
-    else if (warm)                                                                                                              \
-      hipLaunchKernelGGL((balance_robot_params_kernel<PERLEG, true, false>), dim3(grid), dim3(64), 0, st, ctx->d_params, s,      \
-                         batch, d_tau, d_grf, d_status, d_robot_params);                                                        \
-    else                                                                                                                        \
-      hipLaunchKernelGGL((balance_robot_params_kernel<PERLEG, false, false>), dim3(grid), dim3(64), 0, st, ctx->d_params, s,     \
-                         batch, d_tau, d_grf, d_status, d_robot_params);                                                        \
-  } while (0)
-  if (s.normals) QL_LAUNCH_ROBOT_PARAMS(true);
-  else QL_LAUNCH_ROBOT_PARAMS(false);
-#undef QL_LAUNCH_ROBOT_PARAMS
+  const auto kernel = s.normals ? (table  ? balance_robot_params_kernel<true, true, true>
+                                   : warm ? balance_robot_params_kernel<true, true, false>
+                                          : balance_robot_params_kernel<true, false, false>)
+                                : (table  ? balance_robot_params_kernel<false, true, true>
+                                   : warm ? balance_robot_params_kernel<false, true, false>
+                                          : balance_robot_params_kernel<false, false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, s, batch, d_tau, d_grf, d_status, d_robot_params);
   return hipGetLastError() == hipSuccess ? QLAMD_OK : QLAMD_ERR_HIP;
 }
 
@@ -1194,33 +779,6 @@ int qlamd_place_next_call(qlamd_context *ctx, const qlamd_placement *placement) 
   return QLAMD_OK;
 }
 
-int qlamd_placement_from_iterations(qlamd_context *ctx, const int32_t *iterations, int64_t batch, int policy,
-                                    int32_t *robot_order, int memory, void *stream) {
-  if (!ctx || !iterations || !robot_order || batch < 0 || batch > INT32_MAX) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (!valid_policy(policy)) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (memory != QLAMD_MEM_DEVICE && memory != QLAMD_MEM_HOST) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (batch == 0) return QLAMD_OK;
-  if (policy == QLAMD_PLACEMENT_NONE) { // the batch order
-    if (memory == QLAMD_MEM_HOST) {
-      for (int64_t i = 0; i < batch; i++) robot_order[i] = (int32_t)i;
-      return QLAMD_OK;
-    }
-    if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
-    QL_ENTER(ctx, (hipStream_t)stream);
-    return placement_launch(ctx, nullptr, batch, QLAMD_PLACEMENT_NONE, robot_order, (hipStream_t)stream);
-  }
-  if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
-  hipStream_t st = (hipStream_t)stream;
-  QL_ENTER(ctx, st);
-  const size_t B = (size_t)batch;
-  Staged sg(memory == QLAMD_MEM_HOST);
-  sg.in(iterations, B * 4);
-  sg.out(robot_order, B * 4);
-  if (const int rc = sg.upload(ctx, st)) return rc;
-  if (const int rc = launch_placement(ctx, iterations, batch, throughput_policy(policy, batch) ? 1 : 0, robot_order, st)) return rc;
-  return sg.finish(st);
-}
-
 int qlamd_virtual_wrench_batch(qlamd_context *ctx, const qlamd_state_batch *in, int64_t batch, double *wrench,
                                int memory, void *stream) {
   if (!ctx || !in || batch < 0 || !wrench) return QLAMD_ERR_INVALID_ARGUMENT;
@@ -1233,10 +791,7 @@ int qlamd_virtual_wrench_batch(qlamd_context *ctx, const qlamd_state_batch *in, 
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
   const size_t B = (size_t)batch;
-  StatePtrs s{}; // only the base state enters the wrench (virtual_wrench_kernel)
-  s.pos = in->base_position; s.quat = in->base_orientation; s.linvel = in->base_linear_velocity;
-  s.angvel = in->base_angular_velocity; s.dpos = in->desired_position; s.dquat = in->desired_orientation;
-  s.dlinvel = in->desired_linear_velocity; s.dangvel = in->desired_angular_velocity;
+  StatePtrs s = state_ptrs(ctx, *in, qlamd_placement{}); // only the base state enters the wrench (virtual_wrench_kernel)
   Staged sg(memory == QLAMD_MEM_HOST);
   sg.in(s.pos, B * 24); sg.in(s.quat, B * 32); sg.in(s.linvel, B * 24); sg.in(s.angvel, B * 24);
   sg.in(s.dpos, B * 24); sg.in(s.dquat, B * 32); sg.in(s.dlinvel, B * 24); sg.in(s.dangvel, B * 24);

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "balance_core.hpp"
+#include "launch_form.hpp" // QLAMD_THROUGHPUT_BATCH
 #include "qlamd.h"
 
 struct qlamd_context {
@@ -199,9 +200,6 @@ int balance_launch(qlamd_context *ctx, const qlamd_state_batch &in, int layout, 
                    int support_only, const qlamd_placement &pl, int64_t batch, double *joint_effort, double *contact_force,
                    int32_t *status, hipStream_t st);
 
-#ifndef QLAMD_THROUGHPUT_BATCH
-#define QLAMD_THROUGHPUT_BATCH 16384 // robots from which the three-wavefront form of the balance kernel runs
-#endif
 inline bool valid_policy(int policy) {
   return policy == QLAMD_PLACEMENT_AUTO || policy == QLAMD_PLACEMENT_LATENCY || policy == QLAMD_PLACEMENT_THROUGHPUT ||
          policy == QLAMD_PLACEMENT_NONE;

@@ -132,36 +132,49 @@ struct TickSwingArgs {
 // The second attempt of the balance rows whose warm start was rejected: the cold step as a function of its own that ends the
 // wavefront and fetches the kernel's arguments again (balance_kernel.hip, balance_cold_retry, has the reasons).
 struct TickSolveArgs { const DeviceParams *Pp; coop::CoopPtrs cp; int64_t B; double *effort; int32_t *status; }; // the kernel's first parameters
-__device__ __attribute__((noinline, noreturn)) void tick_cold_retry(const TickSolveArgs *args, double *tab, double *rows, double *nrm, bool rejected) {
+// kTable: the caller is tick_table_kernel, whose first attempt has left 0 in the table's slot of a rejected robot -- and nothing
+// else is to be written back
+template <bool kTable>
+__device__ __forceinline__ void tick_retry_body(const TickSolveArgs *args, double *tab, double *rows, double *nrm, bool rejected) {
   const TickSolveArgs &a = *args;
   const int row = threadIdx.x >> 4;
-  int64_t ir = (int64_t)blockIdx.x * 4 + row;
-  if (ir >= a.B) ir = a.B - 1;
+  bool inside;
+  const int64_t ir = coop::slot_robot((int64_t)blockIdx.x * 4 + row, a.B, nullptr, inside);
   coop::CoopPtrs cold = a.cp;
-  cold.prev_working_set = nullptr; cold.working_set = nullptr; cold.warm_retries = nullptr;
-  (void)coop::coop_robot<false, 64, false>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.effort, nullptr, a.status);
-  if (rejected && (threadIdx.x & 15) == 0 && a.cp.working_set) a.cp.working_set[ir] = 0u;
+  cold.prev_working_set = nullptr; cold.working_set = nullptr; cold.warm_retries = nullptr; cold.set_memory = nullptr;
+  (void)coop::coop_robot<coop::CoopForm<>>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.effort, nullptr, a.status);
+  if constexpr (!kTable) {
+    if (rejected && (threadIdx.x & 15) == 0 && a.cp.working_set) a.cp.working_set[ir] = 0u;
+  }
+}
+__device__ __attribute__((noinline, noreturn)) void tick_cold_retry(const TickSolveArgs *args, double *tab, double *rows, double *nrm, bool rejected) {
+  tick_retry_body<false>(args, tab, rows, nrm, rejected);
   __builtin_amdgcn_endpgm();
 }
-template <bool kWarm>
-__global__ __launch_bounds__(64, 2) void tick_solve_kernel(const DeviceParams *__restrict__ Pp, const coop::CoopPtrs cp, int64_t B,
-                                                           double *__restrict__ effort, int32_t *__restrict__ status,
-                                                           unsigned nbal, const TickSwingArgs sw) {
+__device__ __attribute__((noinline, noreturn)) void tick_table_retry(const TickSolveArgs *args, double *tab, double *rows, double *nrm, bool rejected) {
+  tick_retry_body<true>(args, tab, rows, nrm, rejected);
+  __builtin_amdgcn_endpgm();
+}
+// The launch: kWarm: the balance blocks start from cp.prev_working_set, and a rejected warm start is solved again cold by the same
+// wavefront (balance_kernel.hip, balance_coop_kernel); kTable (with kWarm): from the table, cp.set_memory
+template <bool kWarm, bool kTable>
+__device__ __forceinline__ void tick_solve_body(const DeviceParams *Pp, const coop::CoopPtrs &cp, int64_t B, double *effort, int32_t *status,
+                                                unsigned nbal, const TickSwingArgs &sw) {
   __shared__ double tab[4 * kTabPerLeg];
   __shared__ double rows[4 * coop::kCoopLdsDoubles];
   __shared__ double nrm[coop::kCoopNrmDoubles];
   QL_BLOCK_STAMP(2);
   if (blockIdx.x < nbal) {
     const int row = threadIdx.x >> 4;
-    int64_t i = (int64_t)blockIdx.x * 4 + row;
-    const bool live = i < B;
-    if (!live) i = B - 1;
-    const bool rejected = coop::coop_robot<false, 64, kWarm>(*Pp, cp, i, live, tab, rows + row * coop::kCoopLdsDoubles, nrm, effort, nullptr, status);
+    bool live;
+    const int64_t i = coop::slot_robot((int64_t)blockIdx.x * 4 + row, B, nullptr, live);
+    using Form = coop::CoopForm<coop::WarmStart<kWarm>, coop::FromTable<kTable>>;
+    const bool rejected = coop::coop_robot<Form>(*Pp, cp, i, live, tab, rows + row * coop::kCoopLdsDoubles, nrm, effort, nullptr, status);
     if constexpr (kWarm) {
-      // a rejected warm start is solved again cold by the same wavefront (balance_kernel.hip, balance_coop_kernel)
       if (__builtin_expect(Pp->warm_fallback && __builtin_amdgcn_ballot_w64(rejected) != 0ull, 0)) {
         __syncthreads();
-        tick_cold_retry(coop::kernel_arguments_again<TickSolveArgs>(), tab, rows, nrm, rejected);
+        if constexpr (kTable) tick_table_retry(coop::kernel_arguments_again<TickSolveArgs>(), tab, rows, nrm, rejected);
+        else tick_cold_retry(coop::kernel_arguments_again<TickSolveArgs>(), tab, rows, nrm, rejected);
       }
     }
   } else {
@@ -169,46 +182,22 @@ __global__ __launch_bounds__(64, 2) void tick_solve_kernel(const DeviceParams *_
   }
   QL_BLOCK_STAMP(3);
 }
-
-using TickSolveLayout = KernargLayout<decltype(&tick_solve_kernel<true>)>;
-QL_KERNARG_MIRROR(TickSolveLayout, TickSolveArgs, false, Pp, cp, B, effort, status); // (a prefix: the swing blocks' arguments follow)
-
-// The same launch with the balance blocks warm-started from the table (qlamd_tick_batch::set_memory, cp.set_memory): a kernel of
-// its own, so that a tick without the table runs what it ran before the table existed, and a second attempt of its own
-// (balance_kernel.hip, balance_table_retry, has the reason).  The first attempt has left 0 in the slot of a rejected robot.
-__device__ __attribute__((noinline, noreturn)) void tick_table_retry(const TickSolveArgs *args, double *tab, double *rows, double *nrm, bool rejected) {
-  const TickSolveArgs &a = *args;
-  const int row = threadIdx.x >> 4;
-  int64_t ir = (int64_t)blockIdx.x * 4 + row;
-  if (ir >= a.B) ir = a.B - 1;
-  coop::CoopPtrs cold = a.cp;
-  cold.prev_working_set = nullptr; cold.working_set = nullptr; cold.warm_retries = nullptr; cold.set_memory = nullptr;
-  (void)coop::coop_robot<false, 64, false>(*a.Pp, cold, ir, rejected, tab, rows + row * coop::kCoopLdsDoubles, nrm, a.effort, nullptr, a.status);
-  __builtin_amdgcn_endpgm();
+template <bool kWarm>
+__global__ __launch_bounds__(64, 2) void tick_solve_kernel(const DeviceParams *__restrict__ Pp, const coop::CoopPtrs cp, int64_t B,
+                                                           double *__restrict__ effort, int32_t *__restrict__ status,
+                                                           unsigned nbal, const TickSwingArgs sw) {
+  tick_solve_body<kWarm, false>(Pp, cp, B, effort, status, nbal, sw);
 }
+// The same launch with the balance blocks warm-started from the table (qlamd_tick_batch::set_memory): a kernel of its own, so that
+// a tick without the table runs what it ran before the table existed, and a second attempt of its own (balance_kernel.hip,
+// balance_table_retry, has the reason).  The first attempt has left 0 in the slot of a rejected robot.
 __global__ __launch_bounds__(64, 2) void tick_table_kernel(const DeviceParams *__restrict__ Pp, const coop::CoopPtrs cp, int64_t B,
                                                            double *__restrict__ effort, int32_t *__restrict__ status,
                                                            unsigned nbal, const TickSwingArgs sw) {
-  __shared__ double tab[4 * kTabPerLeg];
-  __shared__ double rows[4 * coop::kCoopLdsDoubles];
-  __shared__ double nrm[coop::kCoopNrmDoubles];
-  QL_BLOCK_STAMP(2);
-  if (blockIdx.x < nbal) {
-    const int row = threadIdx.x >> 4;
-    int64_t i = (int64_t)blockIdx.x * 4 + row;
-    const bool live = i < B;
-    if (!live) i = B - 1;
-    const bool rejected = coop::coop_robot<false, 64, true, false, false, true, true>(*Pp, cp, i, live, tab, rows + row * coop::kCoopLdsDoubles, nrm, effort,
-                                                                                     nullptr, status);
-    if (__builtin_expect(Pp->warm_fallback && __builtin_amdgcn_ballot_w64(rejected) != 0ull, 0)) {
-      __syncthreads();
-      tick_table_retry(coop::kernel_arguments_again<TickSolveArgs>(), tab, rows, nrm, rejected);
-    }
-  } else {
-    swing_branch_block(*Pp, sw.SP, sw.pid, sw.s, sw.b, sw.period, B, effort, (int64_t)(blockIdx.x - nbal), tab);
-  }
-  QL_BLOCK_STAMP(3);
+  tick_solve_body<true, true>(Pp, cp, B, effort, status, nbal, sw);
 }
+using TickSolveLayout = KernargLayout<decltype(&tick_solve_kernel<true>)>;
+QL_KERNARG_MIRROR(TickSolveLayout, TickSolveArgs, false, Pp, cp, B, effort, status); // (a prefix: the swing blocks' arguments follow)
 using TickTableLayout = KernargLayout<decltype(&tick_table_kernel)>;
 QL_KERNARG_MIRROR(TickTableLayout, TickSolveArgs, false, Pp, cp, B, effort, status);
 
@@ -1212,15 +1201,8 @@ int qlamd_full_tick_batch(qlamd_context *ctx, const qlamd_swing_params *swing, c
     cp.iterations = d.iterations;
     cp.set_memory = d.set_memory;
     const unsigned nbal = (unsigned)((batch + 3) / 4), nsw = (unsigned)((4 * batch + 63) / 64);
-    if (d.set_memory)
-      hipLaunchKernelGGL(tick_table_kernel, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort, d.status, nbal,
-                         ta);
-    else if (d.working_set)
-      hipLaunchKernelGGL(tick_solve_kernel<true>, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort,
-                         d.status, nbal, ta);
-    else
-      hipLaunchKernelGGL(tick_solve_kernel<false>, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort,
-                         d.status, nbal, ta);
+    const auto kernel = d.set_memory ? tick_table_kernel : d.working_set ? tick_solve_kernel<true> : tick_solve_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nbal + nsw), dim3(64), 0, st, ctx->d_params, cp, batch, d.joint_effort, d.status, nbal, ta);
     if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   } else {
     // two launches (large batches; the one-lane balance kernels of qlamd_set_robots_per_wave, cross-checks)

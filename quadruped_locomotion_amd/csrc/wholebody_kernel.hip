@@ -343,9 +343,7 @@ __device__ __forceinline__ bool wholebody_robot(const DeviceParams &P, const coo
   double nWl[3] = {0.0, 0.0, 1.0};
   if (kPerLeg) { nWl[0] = s.normals[12 * i + 3 * leg]; nWl[1] = s.normals[12 * i + 3 * leg + 1]; nWl[2] = s.normals[12 * i + 3 * leg + 2]; }
   ts.commit(tab);
-  const unsigned stance_legs = live ? (((sm & 0xFFu) ? 1u : 0u) | ((sm & 0xFF00u) ? 2u : 0u) | ((sm & 0xFF0000u) ? 4u : 0u) |
-                                       ((sm & 0xFF000000u) ? 8u : 0u))
-                                    : 0u;
+  const unsigned stance_legs = live ? support_mask(sm) : 0u;
   const int nS = __popc(stance_legs);
   const unsigned mem_slot = QLAMD_SET_MEMORY_SLOT(stance_legs);
   if constexpr (kTable) warm_set = mem_slot == 0u ? mem01.x : mem_slot == 1u ? mem01.y : mem_slot == 2u ? mem23.x : mem23.y;
@@ -470,14 +468,21 @@ __device__ __forceinline__ bool wholebody_robot(const DeviceParams &P, const coo
 // The second attempt of the rows whose warm start was rejected: the cold step as a function of its own that ends the wavefront and
 // fetches the kernel's arguments again (balance_kernel.hip, balance_cold_retry, has the reasons).
 struct WbSolveArgs { const DeviceParams *Pp; coop::WbParamsDev W; WbPtrs s; int64_t B; double *tau, *grf; int32_t *status; PlacePtrs pp; };
-template <bool kPerLeg>
-__device__ __attribute__((noinline, noreturn)) void wholebody_cold_retry(const WbSolveArgs *args, double *lds, bool rejected) {
-  const WbSolveArgs &a = *args;
+// Args: the calling kernel's parameters (WbSolveArgs, or WbTableArgs below); identity_again: the slots write identity_out once more
+// (what wholebody_cold_retry always did; wholebody_table_retry leaves it to the first attempt)
+template <bool kPerLeg, class Args>
+__device__ __forceinline__ void wholebody_retry_body(const Args *args, double *lds, bool rejected, bool identity_again) {
+  const Args &a = *args;
   bool inside;
-  const int64_t i = placed_index(a.pp, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4), a.B, inside);
+  const PlacePtrs index_only{a.pp.order, nullptr, nullptr, nullptr, nullptr};
+  const int64_t i = placed_index(identity_again ? a.pp : index_only, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4), a.B, inside);
   const PlacePtrs cold{a.pp.order, a.pp.iterations, nullptr, nullptr, nullptr};
   (void)wholebody_robot<kPerLeg, false>(*a.Pp, a.W, a.s, i, rejected, a.tau, a.grf, a.status, cold, lds);
-  if (rejected && (threadIdx.x & 15) == 0 && a.pp.working_set) a.pp.working_set[i] = 0ull;
+  if (rejected && (threadIdx.x & 15) == 0 && a.pp.working_set) a.pp.working_set[i] = 0ull; // (its slot of the table, if any, holds 0 already)
+}
+template <bool kPerLeg>
+__device__ __attribute__((noinline, noreturn)) void wholebody_cold_retry(const WbSolveArgs *args, double *lds, bool rejected) {
+  wholebody_retry_body<kPerLeg>(args, lds, rejected, true);
   __builtin_amdgcn_endpgm();
 }
 
@@ -504,13 +509,7 @@ __global__ __launch_bounds__(64, 2) void wholebody_solve_kernel(const DevicePara
 struct WbTableArgs { const DeviceParams *Pp; coop::WbParamsDev W; WbPtrs s; int64_t B; double *tau, *grf; int32_t *status; PlacePtrs pp; unsigned long long *set_memory; };
 template <bool kPerLeg>
 __device__ __attribute__((noinline, noreturn)) void wholebody_table_retry(const WbTableArgs *args, double *lds, bool rejected) {
-  const WbTableArgs &a = *args;
-  bool inside;
-  const PlacePtrs index_only{a.pp.order, nullptr, nullptr, nullptr, nullptr}; // (the first attempt wrote identity_out)
-  const int64_t i = placed_index(index_only, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4), a.B, inside);
-  const PlacePtrs cold{a.pp.order, a.pp.iterations, nullptr, nullptr, nullptr};
-  (void)wholebody_robot<kPerLeg, false>(*a.Pp, a.W, a.s, i, rejected, a.tau, a.grf, a.status, cold, lds);
-  if (rejected && (threadIdx.x & 15) == 0 && a.pp.working_set) a.pp.working_set[i] = 0ull; // (its slot of the table holds 0 already)
+  wholebody_retry_body<kPerLeg>(args, lds, rejected, false);
   __builtin_amdgcn_endpgm();
 }
 template <bool kPerLeg>
@@ -586,14 +585,10 @@ int qlamd_wholebody_dynamics_batch(qlamd_context *ctx, const qlamd_wholebody_bat
   if (leg_form) {
     // one lane per leg, 16 robots per wavefront; M, then h and Jc, from one launch
     const dim3 grid((unsigned)((batch + 15) / 16));
-    if (dM && (dh || dJ))
-      hipLaunchKernelGGL((wholebody_dynamics_leg_kernel<true, true>), grid, dim3(64), 0, st, ctx->d_params, W, s, batch, dM, dh, dJ);
-    else if (dM)
-      hipLaunchKernelGGL((wholebody_dynamics_leg_kernel<true, false>), grid, dim3(64), 0, st, ctx->d_params, W, s, batch, dM,
-                         (double *)nullptr, (double *)nullptr);
-    else
-      hipLaunchKernelGGL((wholebody_dynamics_leg_kernel<false, true>), grid, dim3(64), 0, st, ctx->d_params, W, s, batch,
-                         (double *)nullptr, dh, dJ);
+    const auto kernel = dM && (dh || dJ) ? wholebody_dynamics_leg_kernel<true, true>
+                        : dM             ? wholebody_dynamics_leg_kernel<true, false>
+                                         : wholebody_dynamics_leg_kernel<false, true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, ctx->d_params, W, s, batch, dM, dh, dJ);
   } else {
     // 16 lanes per robot, 4 robots per wavefront
     const dim3 grid((unsigned)((batch + 3) / 4));
@@ -651,21 +646,15 @@ static int wholebody_solve_impl(qlamd_context *ctx, const qlamd_wholebody_params
   const coop::WbParamsDev W = wb_params_of(ctx, params->torque_weight, params->torque_limit, params->gravity);
   const unsigned grid = (unsigned)((batch + 3) / 4);
   const bool warm = pp.prev_working_set || pp.working_set;
-#define QL_LAUNCH_WB(PERLEG)                                                                                                   \
-  do {                                                                                                                         \
-    if (set_memory)                                                                                                            \
-      hipLaunchKernelGGL((wholebody_table_kernel<PERLEG>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,            \
-                         joint_effort, contact_force, status, pp, set_memory);                                                 \
-    else if (warm)                                                                                                             \
-      hipLaunchKernelGGL((wholebody_solve_kernel<PERLEG, true>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,      \
-                         joint_effort, contact_force, status, pp);                                                             \
-    else                                                                                                                       \
-      hipLaunchKernelGGL((wholebody_solve_kernel<PERLEG, false>), dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch,     \
-                         joint_effort, contact_force, status, pp);                                                             \
-  } while (0)
-  if (s.normals) QL_LAUNCH_WB(true);
-  else QL_LAUNCH_WB(false);
-#undef QL_LAUNCH_WB
+  // which kernel: with per-leg normals or without; from the table (a parameter more), warm-started from one set, or cold
+  if (set_memory) {
+    const auto kernel = s.normals ? wholebody_table_kernel<true> : wholebody_table_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch, joint_effort, contact_force, status, pp, set_memory);
+  } else {
+    const auto kernel = s.normals ? (warm ? wholebody_solve_kernel<true, true> : wholebody_solve_kernel<true, false>)
+                                  : (warm ? wholebody_solve_kernel<false, true> : wholebody_solve_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, ctx->d_params, W, s, batch, joint_effort, contact_force, status, pp);
+  }
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   { const int rc = finish_placement(ctx, pl, batch, st); if (rc != QLAMD_OK) return rc; }
   return sg.finish(st);
