@@ -834,6 +834,49 @@ int qlamd_wholebody_solve_placed_batch(qlamd_context *ctx, const qlamd_wholebody
                                        uint64_t *set_memory, double *joint_effort, double *contact_force, int32_t *status,
                                        int memory, void *stream);
 
+/* The plant step: contact-constrained forward dynamics of the same model, and optionally one step of its state.  With
+ * S = the legs flagged in in->support_leg and Js the rows of Jc of those feet, per robot
+ *     M nu' - Js' f = [0 ; tau] + g_ext - h
+ *     Js nu' = -gamma
+ * gamma: the classical acceleration of each flagged foot point at nu' = 0, base coordinates --
+ * w x v + w x (w x r) + 2 w x (J_leg qd) + J_leg' qd (J_leg' the time derivative) -- so that the flagged feet have zero
+ * acceleration in the world.  The contacts are HARD constraints on the flagged feet: no contact detection, no friction
+ * limit, no drift stabilisation -- f may pull.  No leg flagged, or in->support_leg NULL: free flight, f = 0 and
+ * nu' = M^-1 (...).  in->desired_* and in->surface_normal are ignored.
+ *   joint_effort      [B][12]          tau
+ *   generalized_force [B][18] or NULL  g_ext, in the order of nu (added to the right-hand side as it is)
+ *   base_position     [B][3]           world; needed (and read) only with `next`
+ *   acceleration      [B][18] or NULL  out, nu'
+ *   contact_force     [B][12] or NULL  out, f by leg in base coordinates; an unflagged leg's entries are 0
+ *   status            [B]              out: QLAMD_STATUS_OK, or QLAMD_STATUS_NOT_PD when a pivot of M or of Js M^-1 Js' is
+ *                                      not positive or a value is not finite
+ *   next              or NULL (accelerations only): the state after `dt`, semi-implicit Euler --
+ *                         nu+   = nu + dt nu'                         (v+, w+ in base coordinates, qd+)
+ *                         q+    = q + dt qd+
+ *                         quat+ = normalise(quat (x) exp(dt w+))      exp(phi) = (cos(|phi|/2), sin(|phi|/2) phi/|phi|), exactly
+ *                         pos+  = pos + dt R(quat) v+
+ *                         world linear velocity+ = R(quat+) v+
+ *                     All six arrays must be given; each may be the array the state came from (a rollout in place).
+ * A robot whose status is not QLAMD_STATUS_OK: its acceleration and contact_force entries are 0 and its next state is its
+ * state as it came, or (QLAMD_ON_FAILURE_KEEP) all of them stay untouched.
+ * Refused with QLAMD_ERR_INVALID_ARGUMENT, nothing written: joint_effort or status NULL; next given and base_position NULL,
+ * one of its arrays NULL, or dt not finite or not positive; batch negative.  Memory spaces, streams and QLAMD_ERR_BUSY as
+ * for qlamd_wholebody_solve_batch; a QLAMD_MEM_DEVICE call uses no scratch of the context's and can be captured into a
+ * hipGraph with or without qlamd_reserve. */
+#define QLAMD_HAS_PLANT_STEP 1 /* (the feature test: the version number did not move with this entry) */
+typedef struct qlamd_plant_next {       /* all optional as a group: NULL struct = accelerations only */
+  double *joint_position, *joint_velocity;              /* [B][12] */
+  double *base_position;                                /* [B][3]  in: may alias the input */
+  double *base_orientation;                             /* [B][4]  normalised */
+  double *base_linear_velocity, *base_angular_velocity; /* [B][3] world / base, like qlamd_wholebody_batch */
+} qlamd_plant_next;
+
+int qlamd_wholebody_forward_dynamics_batch(qlamd_context *ctx, const qlamd_wholebody_batch *in,
+        const double *joint_effort /*[B][12]*/, const double *generalized_force /*[B][18] or NULL*/,
+        const double *base_position /*[B][3], needed only with next*/, double gravity, double dt,
+        int64_t batch, double *acceleration /*[B][18] or NULL*/, double *contact_force /*[B][12] or NULL*/,
+        const qlamd_plant_next *next /*or NULL*/, int32_t *status, int memory, void *stream);
+
 /* ---- the whole control tick in one call (SURVEY.md section 8 row a1 with rows f1 and f2) -----------------------
  * What the plugin does between one /desired_robot_state message and 12 effort commands:
  *   baseCommandCallback (ros_balance_controller.cpp:761-1083)   message -> desired base state, leg modes, targets

@@ -10,7 +10,8 @@ import subprocess
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB = os.path.join(_PKG, "libqlamd.so")
-SOURCE_NAMES = ("balance_kernel.hip", "pose_kernel.hip", "tick_kernel.hip", "wholebody_kernel.hip")
+SOURCE_NAMES = ("balance_kernel.hip", "pose_kernel.hip", "tick_kernel.hip", "wholebody_kernel.hip",
+                "plant_kernel.hip")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in SOURCE_NAMES]
 OBJ_DIR = os.path.join(_PKG, "csrc", "_obj")
 # Code-generation flags per translation unit.  The active-set kernels are single-wavefront latency problems (a

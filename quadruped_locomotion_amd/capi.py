@@ -32,6 +32,7 @@ EXPORTS = (
     "qlamd_reserve", "qlamd_balance_solve_placed_batch", "qlamd_force_distribution_placed_batch",
     "qlamd_placement_from_iterations", "qlamd_place_next_call", "qlamd_get_counter", "qlamd_set_memory_slot",
     "qlamd_wholebody_solve_placed_batch", "qlamd_robot_params_fill", "qlamd_balance_solve_robot_params_batch",
+    "qlamd_wholebody_forward_dynamics_batch",
 )
 
 
@@ -1057,6 +1058,68 @@ def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, st
             C.c_void_p(stream) if stream else None)
     if rc != OK:
         raise QlamdError(rc, "qlamd_wholebody_solve_placed_batch")
+
+
+class PlantNext(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "base_position", "base_orientation",
+                                           "base_linear_velocity", "base_angular_velocity")]
+
+
+# field of qlamd_plant_next -> (key of the state dict, elements per robot)
+PLANT_NEXT_FIELDS = (("joint_position", "q", 12), ("joint_velocity", "qd", 12), ("base_position", "base_pos", 3),
+                     ("base_orientation", "base_quat", 4), ("base_linear_velocity", "base_linvel", 3),
+                     ("base_angular_velocity", "base_angvel", 3))
+
+
+def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream):
+    fn = lib().qlamd_wholebody_forward_dynamics_batch
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_void_p,
+                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    rc = fn(ctx._h, C.addressof(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B, _ptr(acc), _ptr(f),
+            C.addressof(nxt) if nxt is not None else None, _ptr(status), memory, C.c_void_p(stream) if stream else None)
+    if rc != OK:
+        raise QlamdError(rc, "qlamd_wholebody_forward_dynamics_batch")
+
+
+def wholebody_forward_dynamics(ctx, state, tau, g_ext=None, gravity=9.81, dt=None, free_flight=False, in_place=False):
+    """qlamd_wholebody_forward_dynamics_batch on host buffers -> dict with acc [B,18], f [B,12], status [B] and, with dt, `next`:
+    the state after dt under the keys of `state` (q, qd, base_pos, base_quat, base_linvel, base_angvel).  state["stance"] flags the
+    held feet (free_flight: support_leg = NULL); in_place: the next state is written over `state`'s own arrays."""
+    keep = []
+    B = state["q"].shape[0]
+    if in_place:
+        for _, key, n in PLANT_NEXT_FIELDS:
+            a = state[key]
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags["C_CONTIGUOUS"] and a.size == B * n):
+                raise ValueError("in_place needs state[%r] as a C-contiguous float64 array of %d x %d" % (key, B, n))
+    wb = _wholebody_batch(state, keep)
+    if free_flight:
+        wb.support_leg = None
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    g_ext = None if g_ext is None else np.ascontiguousarray(g_ext, dtype=np.float64)
+    if tau.shape != (B, 12) or (g_ext is not None and g_ext.shape != (B, 18)):
+        raise ValueError("tau must be [%d, 12] and g_ext [%d, 18]" % (B, B))
+    out = dict(acc=np.zeros((B, 18)), f=np.zeros((B, 12)), status=np.full(B, -1, np.int32))
+    nxt, pos = None, None
+    if dt is not None:
+        pos = np.ascontiguousarray(state["base_pos"], dtype=np.float64)
+        out["next"] = {key: (state[key] if in_place else np.zeros((B, n))) for _, key, n in PLANT_NEXT_FIELDS}
+        nxt = PlantNext(*[_ptr(out["next"][key]) for _, key, _ in PLANT_NEXT_FIELDS])
+    _plant_call(ctx, wb, B, tau, g_ext, pos, float(gravity), float(dt) if dt is not None else 0.0, out["acc"], out["f"], nxt,
+                out["status"], MEM_HOST, None)
+    return out
+
+
+def wholebody_forward_dynamics_device(ctx, dstate, tau, status, acc=None, f=None, g_ext=None, gravity=9.81, dt=0.0, next=None,
+                                      free_flight=False, stream=None):
+    """Same entry on torch CUDA tensors; asynchronous.  next: dict of tensors under the state's keys (q, qd, base_pos, base_quat,
+    base_linvel, base_angvel) or NULL; it may be `dstate` itself, which then needs "base_pos" (a rollout in place)."""
+    wb = _wholebody_batch(dstate, [])
+    if free_flight:
+        wb.support_leg = None
+    nxt = None if next is None else PlantNext(*[_ptr(next[key]) for _, key, _ in PLANT_NEXT_FIELDS])
+    _plant_call(ctx, wb, dstate["q"].shape[0], tau, g_ext, dstate.get("base_pos") if next is not None else None, float(gravity),
+                float(dt), acc, f, nxt, status, MEM_DEVICE, stream)
 
 
 def wholebody_dynamics_device(ctx, dstate, M, h, Jc, gravity=9.81, stream=None):

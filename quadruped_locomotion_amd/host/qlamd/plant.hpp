@@ -1,0 +1,70 @@
+// The plant step from C++: the state of a batch of robots on the host and qlamd_wholebody_forward_dynamics_batch on it, in
+// place -- what a simulation loop calls after the controller (balance_controller/WholeBodyController.hpp gives the efforts of
+// one robot, qlamd_wholebody_solve_batch those of a batch).  The contacts are hard constraints on the flagged feet: no contact
+// detection, no friction limit, no drift stabilisation (include/qlamd.h).  Needs qlamd.h only.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "qlamd.h"
+
+#ifndef QLAMD_HAS_PLANT_STEP
+#error "this qlamd.h has no qlamd_wholebody_forward_dynamics_batch"
+#endif
+
+namespace qlamd {
+namespace host {
+
+// The arrays of qlamd_wholebody_batch that describe a state, with the base position, owned
+struct PlantState {
+  explicit PlantState(int64_t batch)
+      : joint_position((size_t)batch * 12), joint_velocity((size_t)batch * 12), base_position((size_t)batch * 3),
+        base_orientation((size_t)batch * 4), base_linear_velocity((size_t)batch * 3), base_angular_velocity((size_t)batch * 3),
+        support_leg((size_t)batch * 4) {
+    for (int64_t i = 0; i < batch; i++) base_orientation[(size_t)i * 4] = 1.0;
+  }
+  int64_t size() const { return (int64_t)(joint_position.size() / 12); }
+  // the state as the input of any whole-body entry (desired_* and surface_normal stay NULL: the plant step ignores them)
+  qlamd_wholebody_batch batch() const {
+    qlamd_wholebody_batch in{};
+    in.joint_position = joint_position.data();
+    in.joint_velocity = joint_velocity.data();
+    in.base_orientation = base_orientation.data();
+    in.base_linear_velocity = base_linear_velocity.data();
+    in.base_angular_velocity = base_angular_velocity.data();
+    in.support_leg = support_leg.data();
+    return in;
+  }
+  std::vector<double> joint_position, joint_velocity;          // [B][12]
+  std::vector<double> base_position;                           // [B][3] world
+  std::vector<double> base_orientation;                        // [B][4] (w, x, y, z)
+  std::vector<double> base_linear_velocity, base_angular_velocity; // [B][3] world / base
+  std::vector<uint8_t> support_leg;                            // [B][4] the feet held by the contact constraints
+};
+
+// nu' [B][18] and f [B][12] for the efforts joint_effort [B][12] (either output may be NULL); the library's return code
+inline int forward_dynamics(qlamd_context *ctx, const PlantState &s, const double *joint_effort, double gravity, double *acceleration,
+                            double *contact_force, int32_t *status, const double *generalized_force = nullptr) {
+  const qlamd_wholebody_batch in = s.batch();
+  return qlamd_wholebody_forward_dynamics_batch(ctx, &in, joint_effort, generalized_force, nullptr, gravity, 0.0, s.size(), acceleration,
+                                                contact_force, nullptr, status, QLAMD_MEM_HOST, nullptr);
+}
+
+// One semi-implicit Euler step of `dt` in place (include/qlamd.h has the rule); contact_force [B][12] or NULL
+inline int step(qlamd_context *ctx, PlantState &s, const double *joint_effort, double gravity, double dt, int32_t *status,
+                double *contact_force = nullptr, const double *generalized_force = nullptr) {
+  const qlamd_wholebody_batch in = s.batch();
+  qlamd_plant_next next;
+  next.joint_position = s.joint_position.data();
+  next.joint_velocity = s.joint_velocity.data();
+  next.base_position = s.base_position.data();
+  next.base_orientation = s.base_orientation.data();
+  next.base_linear_velocity = s.base_linear_velocity.data();
+  next.base_angular_velocity = s.base_angular_velocity.data();
+  return qlamd_wholebody_forward_dynamics_batch(ctx, &in, joint_effort, generalized_force, s.base_position.data(), gravity, dt, s.size(),
+                                                nullptr, contact_force, &next, status, QLAMD_MEM_HOST, nullptr);
+}
+
+} // namespace host
+} // namespace qlamd
