@@ -2,6 +2,10 @@
 
 The arithmetic lives in the HIP kernels of libqlamd.so.  There is no Python or
 CPU fallback: a missing library or a missing GPU raises.
+
+Layout of this file: the header's constants, its structs, its functions (SIGNATURES: the one place an entry's
+restype / argtypes are written), then one helper per marshalling job, then the wrappers.  tests/test_capi_cpu.py holds
+constants, struct layouts and signatures against the header and the C compiler.
 """
 import ctypes as C
 import os
@@ -11,31 +15,29 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libqlamd.so")
 
+# ---- the constants of include/qlamd.h (QLAMD_<name> there), grouped as the header groups them ---------------------------
+# return codes of the API calls
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_LOADED, ERR_OUT_OF_MEMORY, ERR_BUSY, ERR_NEEDS_RESERVE = -1, -2, -3, -4, -5, -6, -7
-STATUS_OK, STATUS_INFEASIBLE, STATUS_NOT_PD, STATUS_MAX_ITER = 0, 1, 2, 3
-STATUS_WARM_REJECTED = 6
+# per-robot status words
+STATUS_OK, STATUS_INFEASIBLE, STATUS_NOT_PD, STATUS_MAX_ITER, STATUS_NO_COMMAND, STATUS_DEPENDENT_EQUALITY, STATUS_WARM_REJECTED = range(7)
+# where caller buffers live
 MEM_DEVICE, MEM_HOST = 0, 1
-
-EXPORTS = (
-    "qlamd_balance_default_params", "qlamd_default_robot_model", "qlamd_context_create",
-    "qlamd_context_destroy", "qlamd_set_robots_per_wave", "qlamd_balance_solve_batch",
-    "qlamd_virtual_wrench_batch", "qlamd_leg_kinematics_batch", "qlamd_strerror", "qlamd_version",
-    "qlamd_qp_solve_batch", "qlamd_pose_default_params", "qlamd_pose_sqp_batch",
-    "qlamd_force_distribution_batch", "qlamd_swing_default_params", "qlamd_swing_leg_torque_batch",
-    "qlamd_pose_qp_batch", "qlamd_pose_check_batch", "qlamd_pose_geometric_batch",
-    "qlamd_base_auto_optimize_pose_batch", "qlamd_leg_state_machine_batch", "qlamd_robot_state_unpack_batch",
-    "qlamd_ik_default_params", "qlamd_leg_inverse_kinematics_batch",
-    "qlamd_joint_pid_default_params", "qlamd_swing_branch_batch",
-    "qlamd_wholebody_default_params", "qlamd_wholebody_dynamics_batch", "qlamd_wholebody_solve_batch",
-    "qlamd_full_tick_batch", "qlamd_set_option", "qlamd_tick_command_bytes", "qlamd_weighted_lsq_qp_batch",
-    "qlamd_reserve", "qlamd_balance_solve_placed_batch", "qlamd_force_distribution_placed_batch",
-    "qlamd_placement_from_iterations", "qlamd_place_next_call", "qlamd_get_counter", "qlamd_set_memory_slot",
-    "qlamd_wholebody_solve_placed_batch", "qlamd_robot_params_fill", "qlamd_balance_solve_robot_params_batch",
-    "qlamd_wholebody_forward_dynamics_batch",
-)
+STATE_RECORD_DOUBLES = 48
+# context options and their values
+OPT_ON_FAILURE, OPT_REFINE_PASSES, OPT_DYNAMICS_FORM, OPT_PLACEMENT_WAIT, OPT_WARM_FALLBACK, OPT_STATE_LAYOUT = 1, 2, 5, 6, 7, 8
+STATE_FIELDS, STATE_RECORDS = 0, 1
+ON_FAILURE_ZERO, ON_FAILURE_KEEP = 0, 1
+DYNAMICS_AUTO, DYNAMICS_LEG, DYNAMICS_ROW = 0, 1, 2
+# event counters
+COUNTER_PLACEMENT_GIVE_UPS, COUNTER_WARM_RETRIES = 0, 1
+# placement policies
+PLACEMENT_AUTO, PLACEMENT_LATENCY, PLACEMENT_THROUGHPUT, PLACEMENT_NONE = 0, 1, 2, 3
+ROBOT_PARAMS_DOUBLES = 32
+NO_BOUND = 1.7976931348623157e308   # std::numeric_limits<double>::max(): what the reference writes for "no bound"
 
 
+# ---- the structs of include/qlamd.h, in its order: class <Name> mirrors qlamd_<name> -------------------------------------
 class BalanceParams(C.Structure):
     _fields_ = [
         ("kp_trans", C.c_double * 3), ("kd_trans", C.c_double * 3), ("kff_trans", C.c_double * 3),
@@ -48,7 +50,39 @@ class BalanceParams(C.Structure):
     ]
 
 
-ROBOT_PARAMS_DOUBLES = 32
+class RobotModel(C.Structure):
+    _fields_ = [
+        ("joint_xyz", ((C.c_double * 3) * 4) * 4), ("joint_rpy", ((C.c_double * 3) * 4) * 4),
+        ("link_mass", (C.c_double * 4) * 4), ("link_com", ((C.c_double * 3) * 4) * 4),
+        ("link_inertia", ((C.c_double * 6) * 4) * 4),
+        ("base_mass", C.c_double), ("base_com", C.c_double * 3), ("base_inertia", C.c_double * 6),
+    ]
+
+
+class StateBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "joint_position", "base_position", "base_orientation", "base_linear_velocity",
+        "base_angular_velocity", "desired_position", "desired_orientation",
+        "desired_linear_velocity", "desired_angular_velocity", "support_leg", "surface_normal")]
+
+
+# state-dict key -> StateBatch field (keys as produced by synth.make_states)
+FIELD_OF_KEY = (
+    ("q", "joint_position", 12), ("base_pos", "base_position", 3), ("base_quat", "base_orientation", 4),
+    ("base_linvel", "base_linear_velocity", 3), ("base_angvel", "base_angular_velocity", 3),
+    ("des_pos", "desired_position", 3), ("des_quat", "desired_orientation", 4),
+    ("des_linvel", "desired_linear_velocity", 3), ("des_angvel", "desired_angular_velocity", 3),
+)
+# offsets (doubles) of the fields inside a qlamd_state_record (include/qlamd.h), by the keys of synth.make_states
+STATE_RECORD_OFFSETS = {"q": 0, "base_pos": 12, "base_quat": 16, "base_linvel": 20, "base_angvel": 23, "des_pos": 26, "des_quat": 30,
+                        "des_linvel": 34, "des_angvel": 37}
+
+
+class Placement(C.Structure):
+    """qlamd_placement"""
+    _fields_ = [("robot_order", C.c_void_p), ("iterations", C.c_void_p), ("prev_iterations", C.c_void_p),
+                ("next_robot_order", C.c_void_p), ("policy", C.c_int), ("prev_working_set", C.c_void_p),
+                ("working_set", C.c_void_p), ("set_memory", C.c_void_p)]
 
 
 class RobotParams(C.Structure):
@@ -62,20 +96,31 @@ class RobotParams(C.Structure):
     ]
 
 
-class Placement(C.Structure):
-    """qlamd_placement"""
-    _fields_ = [("robot_order", C.c_void_p), ("iterations", C.c_void_p), ("prev_iterations", C.c_void_p),
-                ("next_robot_order", C.c_void_p), ("policy", C.c_int), ("prev_working_set", C.c_void_p),
-                ("working_set", C.c_void_p), ("set_memory", C.c_void_p)]
+class SwingParams(C.Structure):
+    _fields_ = [("kp", C.c_double * 3), ("kd", C.c_double * 3), ("period", C.c_double), ("accel_window", C.c_double),
+                ("accel_scale", C.c_double), ("gravity", C.c_double)]
 
 
-class RobotModel(C.Structure):
-    _fields_ = [
-        ("joint_xyz", ((C.c_double * 3) * 4) * 4), ("joint_rpy", ((C.c_double * 3) * 4) * 4),
-        ("link_mass", (C.c_double * 4) * 4), ("link_com", ((C.c_double * 3) * 4) * 4),
-        ("link_inertia", ((C.c_double * 6) * 4) * 4),
-        ("base_mass", C.c_double), ("base_com", C.c_double * 3), ("base_inertia", C.c_double * 6),
-    ]
+class SwingBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "joint_velocity_oldest",
+                                           "target_foot_position", "target_foot_velocity", "support_leg",
+                                           "id_joint_position")]
+
+
+class PoseParams(C.Structure):
+    _fields_ = [("hip_in_base", (C.c_double * 3) * 4), ("com_weight", C.c_double), ("tolerance", C.c_double),
+                ("max_iterations", C.c_int), ("dummy_equality", C.c_int), ("leg_order", C.c_int * 4)]
+
+
+class PoseBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("stance", "stance_mask", "nominal_stance", "support_polygon",
+                                           "n_vertices", "center_of_mass", "max_limb_length", "pose")]
+
+
+# problem-dict key (synth.make_pose_problems) -> PoseBatch field
+POSE_FIELD_OF_KEY = (("stance", "stance"), ("stance_mask", "stance_mask"), ("nominal", "nominal_stance"),
+                     ("polygon", "support_polygon"), ("n_vertices", "n_vertices"), ("r_com", "center_of_mass"),
+                     ("max_len", "max_limb_length"), ("pose", "pose"))
 
 
 class LegStateBatch(C.Structure):
@@ -99,12 +144,44 @@ class RobotStateFields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _ in ROBOT_STATE_FIELDS] + [("support_leg", C.c_void_p), ("leg_mode", C.c_void_p)]
 
 
+class IkParams(C.Structure):
+    _fields_ = [("d", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("limb_config", C.c_uint8 * 4)]
+
+
 class JointPidParams(C.Structure):
     _fields_ = [(n, C.c_double * 12) for n in ("p", "i", "d", "i_max", "i_min", "lower", "upper")] + [("antiwindup", C.c_int)]
 
 
 class SwingBranchExtra(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("base_orientation", "joint_command", "leg_mode", "pid_error_last", "pid_error_integral")]
+
+
+class WholebodyBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "base_orientation", "base_linear_velocity",
+                                           "base_angular_velocity", "desired_base_acceleration",
+                                           "desired_joint_acceleration", "support_leg", "surface_normal")]
+
+
+# key of a synth.make_wholebody_states dict -> field of qlamd_wholebody_batch
+WHOLEBODY_FIELDS = (("q", "joint_position"), ("qd", "joint_velocity"), ("base_quat", "base_orientation"),
+                    ("base_linvel", "base_linear_velocity"), ("base_angvel", "base_angular_velocity"),
+                    ("a_des", "desired_base_acceleration"), ("qdd_des", "desired_joint_acceleration"),
+                    ("stance", "support_leg"), ("normals", "surface_normal"))
+
+
+class WholebodyParams(C.Structure):
+    _fields_ = [("torque_weight", C.c_double), ("torque_limit", C.c_double), ("gravity", C.c_double)]
+
+
+class PlantNext(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "base_position", "base_orientation",
+                                           "base_linear_velocity", "base_angular_velocity")]
+
+
+# field of qlamd_plant_next -> (key of the state dict, elements per robot)
+PLANT_NEXT_FIELDS = (("joint_position", "q", 12), ("joint_velocity", "qd", 12), ("base_position", "base_pos", 3),
+                     ("base_orientation", "base_quat", 4), ("base_linear_velocity", "base_linvel", 3),
+                     ("base_angular_velocity", "base_angvel", 3))
 
 
 TICK_FIELDS = (("messages", np.uint8), ("offsets", np.int64), ("joint_position", np.float64), ("joint_velocity", np.float64),
@@ -120,68 +197,59 @@ class TickBatch(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _ in TICK_FIELDS]
 
 
-class WholebodyBatch(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "base_orientation", "base_linear_velocity",
-                                           "base_angular_velocity", "desired_base_acceleration",
-                                           "desired_joint_acceleration", "support_leg", "surface_normal")]
-
-
-class WholebodyParams(C.Structure):
-    _fields_ = [("torque_weight", C.c_double), ("torque_limit", C.c_double), ("gravity", C.c_double)]
-
-
-# key of a synth.make_wholebody_states dict -> field of qlamd_wholebody_batch
-WHOLEBODY_FIELDS = (("q", "joint_position"), ("qd", "joint_velocity"), ("base_quat", "base_orientation"),
-                    ("base_linvel", "base_linear_velocity"), ("base_angvel", "base_angular_velocity"),
-                    ("a_des", "desired_base_acceleration"), ("qdd_des", "desired_joint_acceleration"),
-                    ("stance", "support_leg"), ("normals", "surface_normal"))
-
-
-class IkParams(C.Structure):
-    _fields_ = [("d", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("limb_config", C.c_uint8 * 4)]
-
-
-class SwingParams(C.Structure):
-    _fields_ = [("kp", C.c_double * 3), ("kd", C.c_double * 3), ("period", C.c_double), ("accel_window", C.c_double),
-                ("accel_scale", C.c_double), ("gravity", C.c_double)]
-
-
-class SwingBatch(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "joint_velocity_oldest",
-                                           "target_foot_position", "target_foot_velocity", "support_leg",
-                                           "id_joint_position")]
-
-
-class StateBatch(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "joint_position", "base_position", "base_orientation", "base_linear_velocity",
-        "base_angular_velocity", "desired_position", "desired_orientation",
-        "desired_linear_velocity", "desired_angular_velocity", "support_leg", "surface_normal")]
-
-
-class PoseParams(C.Structure):
-    _fields_ = [("hip_in_base", (C.c_double * 3) * 4), ("com_weight", C.c_double), ("tolerance", C.c_double),
-                ("max_iterations", C.c_int), ("dummy_equality", C.c_int), ("leg_order", C.c_int * 4)]
-
-
-class PoseBatch(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("stance", "stance_mask", "nominal_stance", "support_polygon",
-                                           "n_vertices", "center_of_mass", "max_limb_length", "pose")]
-
-
-# problem-dict key (synth.make_pose_problems) -> PoseBatch field
-POSE_FIELD_OF_KEY = (("stance", "stance"), ("stance_mask", "stance_mask"), ("nominal", "nominal_stance"),
-                     ("polygon", "support_polygon"), ("n_vertices", "n_vertices"), ("r_com", "center_of_mass"),
-                     ("max_len", "max_limb_length"), ("pose", "pose"))
-
-
-# state-dict key -> StateBatch field (keys as produced by synth.make_states)
-FIELD_OF_KEY = (
-    ("q", "joint_position", 12), ("base_pos", "base_position", 3), ("base_quat", "base_orientation", 4),
-    ("base_linvel", "base_linear_velocity", 3), ("base_angvel", "base_angular_velocity", 3),
-    ("des_pos", "desired_position", 3), ("des_quat", "desired_orientation", 4),
-    ("des_linvel", "desired_linear_velocity", 3), ("des_angvel", "desired_angular_velocity", 3),
-)
+# ---- the functions of include/qlamd.h, in its order: entry -> (restype, argtypes) -----------------------------------------
+# A pointer to a struct is POINTER(mirror) where callers hand over byref(mirror), c_void_p where they hand over addresses
+# (ctypes takes a byref for either); arrays, the context and the stream are c_void_p.
+_p, _int, _i64, _dbl, _ref = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.POINTER
+_where = [_int, _p]     # `memory` and `stream`, the tail of every batch entry
+SIGNATURES = {
+    "qlamd_balance_default_params": (None, [_ref(BalanceParams)]),
+    "qlamd_default_robot_model": (None, [_ref(RobotModel)]),
+    "qlamd_context_create": (_int, [_ref(BalanceParams), _ref(RobotModel), _int, _ref(_p)]),
+    "qlamd_context_destroy": (None, [_p]),
+    "qlamd_reserve": (_int, [_p, _i64]),
+    "qlamd_set_robots_per_wave": (_int, [_p, _int]),
+    "qlamd_set_option": (_int, [_p, _int, _int]),
+    "qlamd_get_counter": (_int, [_p, _int, _ref(_i64)]),
+    "qlamd_balance_solve_batch": (_int, [_p, _ref(StateBatch), _i64, _p, _p, _p] + _where),
+    "qlamd_force_distribution_batch": (_int, [_p] + [_p] * 5 + [_i64, _p, _p, _p] + _where),
+    "qlamd_set_memory_slot": (C.c_uint, [C.c_uint]),
+    "qlamd_balance_solve_placed_batch": (_int, [_p, _ref(StateBatch), _i64, _ref(Placement), _p, _p, _p] + _where),
+    "qlamd_force_distribution_placed_batch": (_int, [_p] + [_p] * 5 + [_i64, _ref(Placement), _p, _p, _p] + _where),
+    "qlamd_robot_params_fill": (_int, [_p, _i64, _p]),
+    "qlamd_balance_solve_robot_params_batch": (_int, [_p, _ref(StateBatch), _p, _i64, _ref(Placement), _p, _p, _p] + _where),
+    "qlamd_place_next_call": (_int, [_p, _ref(Placement)]),
+    "qlamd_placement_from_iterations": (_int, [_p, _p, _i64, _int, _p] + _where),
+    "qlamd_swing_default_params": (None, [_ref(SwingParams)]),
+    "qlamd_swing_leg_torque_batch": (_int, [_p, _ref(SwingParams), _ref(SwingBatch), _i64, _p] + _where),
+    "qlamd_virtual_wrench_batch": (_int, [_p, _ref(StateBatch), _i64, _p] + _where),
+    "qlamd_leg_kinematics_batch": (_int, [_p, _p, _p, _i64, _p, _p, _p] + _where),
+    "qlamd_qp_solve_batch": (_int, [_p, _int, _int, _int] + [_p] * 6 + [_i64, _p, _p, _p] + _where),
+    "qlamd_weighted_lsq_qp_batch": (_int, [_p, _int, _int, _int, _int] + [_p] * 9 + [_i64, _p, _p] + _where),
+    "qlamd_pose_default_params": (None, [_ref(PoseParams)]),
+    "qlamd_pose_sqp_batch": (_int, [_p, _ref(PoseParams), _ref(PoseBatch), _i64, _p, _p, _p] + _where),
+    "qlamd_pose_qp_batch": (_int, [_p, _ref(PoseParams), _ref(PoseBatch), _i64, _p, _p] + _where),
+    "qlamd_pose_check_batch": (_int, [_p, _ref(PoseParams), _ref(PoseBatch), _p, _dbl, _i64, _p] + _where),
+    "qlamd_pose_geometric_batch": (_int, [_p, _ref(PoseParams), _ref(PoseBatch), _p, _i64, _p] + _where),
+    "qlamd_base_auto_optimize_pose_batch": (_int, [_p, _ref(PoseParams), _ref(PoseBatch), _p, _p, _dbl, _i64, _p, _p, _p, _p] + _where),
+    "qlamd_leg_state_machine_batch": (_int, [_p, _ref(LegStateBatch), _int, _i64] + _where),
+    "qlamd_robot_state_unpack_batch": (_int, [_p, _p, _p, _i64, _ref(RobotStateFields), _p] + _where),
+    "qlamd_ik_default_params": (None, [_ref(IkParams)]),
+    "qlamd_leg_inverse_kinematics_batch": (_int, [_p, _ref(IkParams), _p, _p, _i64, _p, _p] + _where),
+    "qlamd_joint_pid_default_params": (None, [_ref(JointPidParams)]),
+    "qlamd_swing_branch_batch": (_int, [_p, _ref(SwingParams), _ref(JointPidParams), _ref(SwingBatch), _ref(SwingBranchExtra), _dbl, _i64,
+                                        _p] + _where),
+    "qlamd_wholebody_default_params": (None, [_ref(WholebodyParams)]),
+    "qlamd_wholebody_dynamics_batch": (_int, [_p, _ref(WholebodyBatch), _dbl, _i64, _p, _p, _p] + _where),
+    "qlamd_wholebody_solve_batch": (_int, [_p, _ref(WholebodyParams), _ref(WholebodyBatch), _i64, _p, _p, _p] + _where),
+    "qlamd_wholebody_solve_placed_batch": (_int, [_p, _p, _p, _i64, _p, _p, _p, _p, _p] + _where),
+    "qlamd_wholebody_forward_dynamics_batch": (_int, [_p, _p, _p, _p, _p, _dbl, _dbl, _i64, _p, _p, _p, _p] + _where),
+    "qlamd_tick_command_bytes": (C.c_size_t, [_i64]),
+    "qlamd_full_tick_batch": (_int, [_p, _ref(SwingParams), _ref(JointPidParams), _ref(TickBatch), _dbl, _int, _i64] + _where),
+    "qlamd_strerror": (C.c_char_p, [_int]),
+    "qlamd_version": (_int, []),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 class QlamdError(RuntimeError):
@@ -208,81 +276,147 @@ def lib():
                 "HIP extension missing: %s (run `python -c 'import __graft_entry__ as g; g.build()'`). "
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.qlamd_strerror.restype = C.c_char_p
-        L.qlamd_strerror.argtypes = [C.c_int]
-        L.qlamd_context_create.argtypes = [C.POINTER(BalanceParams), C.POINTER(RobotModel), C.c_int,
-                                           C.POINTER(C.c_void_p)]
-        L.qlamd_context_destroy.argtypes = [C.c_void_p]
-        L.qlamd_context_destroy.restype = None
-        L.qlamd_set_robots_per_wave.argtypes = [C.c_void_p, C.c_int]
-        if hasattr(L, "qlamd_get_counter"):  # (absent from builds before 0.6: tools/ab runs older libraries through this module)
-            L.qlamd_get_counter.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        if hasattr(L, "qlamd_reserve"):  # (absent from libraries of earlier revisions that tools/experiments/variants.py builds)
-            L.qlamd_reserve.argtypes = [C.c_void_p, C.c_int64]
-        L.qlamd_balance_solve_batch.argtypes = [C.c_void_p, C.POINTER(StateBatch), C.c_int64, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        if hasattr(L, "qlamd_balance_solve_placed_batch"):
-            L.qlamd_balance_solve_placed_batch.argtypes = [C.c_void_p, C.POINTER(StateBatch), C.c_int64, C.POINTER(Placement),
-                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-            L.qlamd_force_distribution_placed_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.POINTER(Placement)] + [
-                C.c_void_p] * 3 + [C.c_int, C.c_void_p]
-            L.qlamd_placement_from_iterations.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
-                                                          C.c_void_p]
-            L.qlamd_place_next_call.argtypes = [C.c_void_p, C.POINTER(Placement)]
-        if hasattr(L, "qlamd_robot_params_fill"):  # (absent from builds before per-robot parameters, which the probes run)
-            L.qlamd_robot_params_fill.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-            L.qlamd_balance_solve_robot_params_batch.argtypes = [C.c_void_p, C.POINTER(StateBatch), C.c_void_p, C.c_int64,
-                                                                 C.POINTER(Placement), C.c_void_p, C.c_void_p, C.c_void_p,
-                                                                 C.c_int, C.c_void_p]
-        if hasattr(L, "qlamd_set_memory_slot"):  # (absent from builds before 0.7, which tools/set_memory_probe.py --lib runs)
-            L.qlamd_set_memory_slot.argtypes = [C.c_uint]
-            L.qlamd_set_memory_slot.restype = C.c_uint
-        L.qlamd_virtual_wrench_batch.argtypes = [C.c_void_p, C.POINTER(StateBatch), C.c_int64, C.c_void_p,
-                                                 C.c_int, C.c_void_p]
-        L.qlamd_leg_kinematics_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_qp_solve_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [
-            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_force_distribution_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_pose_qp_batch.argtypes = [C.c_void_p, C.POINTER(PoseParams), C.POINTER(PoseBatch), C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_pose_check_batch.argtypes = [C.c_void_p, C.POINTER(PoseParams), C.POINTER(PoseBatch), C.c_void_p, C.c_double,
-                                             C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_pose_geometric_batch.argtypes = [C.c_void_p, C.POINTER(PoseParams), C.POINTER(PoseBatch), C.c_void_p, C.c_int64,
-                                                 C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_base_auto_optimize_pose_batch.argtypes = [C.c_void_p, C.POINTER(PoseParams), C.POINTER(PoseBatch), C.c_void_p,
-                                                          C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p,
-                                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_leg_state_machine_batch.argtypes = [C.c_void_p, C.POINTER(LegStateBatch), C.c_int, C.c_int64, C.c_int, C.c_void_p]
-        L.qlamd_robot_state_unpack_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RobotStateFields),
-                                                     C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_ik_default_params.argtypes = [C.POINTER(IkParams)]
-        L.qlamd_ik_default_params.restype = None
-        L.qlamd_leg_inverse_kinematics_batch.argtypes = [C.c_void_p, C.POINTER(IkParams), C.c_void_p, C.c_void_p, C.c_int64,
-                                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_joint_pid_default_params.argtypes = [C.POINTER(JointPidParams)]
-        L.qlamd_joint_pid_default_params.restype = None
-        L.qlamd_swing_branch_batch.argtypes = [C.c_void_p, C.POINTER(SwingParams), C.POINTER(JointPidParams), C.POINTER(SwingBatch),
-                                               C.POINTER(SwingBranchExtra), C.c_double, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_swing_leg_torque_batch.argtypes = [C.c_void_p, C.POINTER(SwingParams), C.POINTER(SwingBatch), C.c_int64,
-                                                   C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_pose_sqp_batch.argtypes = [C.c_void_p, C.POINTER(PoseParams), C.POINTER(PoseBatch), C.c_int64,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_full_tick_batch.argtypes = [C.c_void_p, C.POINTER(SwingParams), C.POINTER(JointPidParams), C.POINTER(TickBatch),
-                                            C.c_double, C.c_int, C.c_int64, C.c_int, C.c_void_p]
-        L.qlamd_wholebody_default_params.argtypes = [C.POINTER(WholebodyParams)]
-        L.qlamd_wholebody_default_params.restype = None
-        L.qlamd_wholebody_dynamics_batch.argtypes = [C.c_void_p, C.POINTER(WholebodyBatch), C.c_double, C.c_int64, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_wholebody_solve_batch.argtypes = [C.c_void_p, C.POINTER(WholebodyParams), C.POINTER(WholebodyBatch), C.c_int64,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.qlamd_weighted_lsq_qp_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [
-            C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            # (an entry may be absent: tools/ab, tools/experiments/variants.py and tools/set_memory_probe.py --lib run builds of
+            # earlier revisions through this module; calling what such a build lacks is an AttributeError there)
+            fn = getattr(L, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
+# ---- one helper per marshalling job ------------------------------------------------------------------------------------------
+def _call(fn, *args):
+    """Call an entry that returns a QLAMD_* code: anything but OK raises QlamdError under the entry's own name."""
+    rc = fn(*args)
+    if rc != OK:
+        raise QlamdError(rc, fn.__name__)
+
+
+def _stream(stream):
+    """hipStream_t handle (an integer, e.g. torch's cuda_stream) or None -> the `stream` argument."""
+    return C.c_void_p(stream) if stream else None
+
+
+def _ptr(a):
+    """data pointer of a numpy array or a torch tensor (None -> NULL)."""
+    if a is None:
+        return None
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+def _filled(mirror, entry):
+    """A parameter struct filled by the library's qlamd_*_default_params / qlamd_default_robot_model."""
+    p = mirror()
+    getattr(lib(), entry)(C.byref(p))
+    return p
+
+
+def _is(a, dtype, count):
+    """a (torch tensor or numpy array) is contiguous and holds `count` elements of `dtype` ("int32", ...)."""
+    contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else a.flags["C_CONTIGUOUS"]
+    return str(a.dtype).split(".")[-1] == dtype and (a.numel() if hasattr(a, "numel") else a.size) == count and contiguous
+
+
+def _host_out(a, B, name):
+    """A caller-supplied host output array the library writes B * 96 bytes into: float64, C-contiguous, [B, 12] -- or a
+    fresh one.  (The library cannot see a numpy array's dtype or strides: a float32 or transposed array would be
+    overrun.)"""
+    if a is None:
+        return np.zeros((B, 12))
+    if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags["C_CONTIGUOUS"] and a.shape == (B, 12)):
+        raise ValueError("%s must be a C-contiguous float64 array of shape (%d, 12)" % (name, B))
+    return a
+
+
+def _state_batch(state, normals, memory, skip=()):
+    """qlamd_state_batch over a state dict (keys of synth.make_states) and `normals` (or None) -> (StateBatch, keep-alives, B).
+    MEM_HOST: every field as a C-contiguous float64 (support flags: uint8) array [B, k], B from the first field; MEM_DEVICE:
+    torch tensors, used in place.  Fields whose key is in `skip` stay NULL."""
+    arrays = dict(state, normals=normals)
+    if normals is None:
+        skip = tuple(skip) + ("normals",)
+    sb, keep, B = StateBatch(), [], None
+    for key, field, k in FIELD_OF_KEY + (("stance", "support_leg", 4), ("normals", "surface_normal", 12)):
+        if key in skip:
+            continue
+        a = arrays[key]
+        if memory == MEM_HOST:
+            a = np.asarray(a, dtype=np.uint8 if key == "stance" else np.float64)
+            a = np.ascontiguousarray(a.reshape(-1 if B is None else B, k))
+            keep.append(a)
+            setattr(sb, field, a.ctypes.data)
+        else:
+            setattr(sb, field, a.data_ptr())
+        if B is None:
+            B = int(a.shape[0])
+    return sb, keep, B
+
+
+def _placement(B, policy=0, order=None, iterations=None, prev_iterations=None, next_order=None, prev_working_set=None,
+               working_set=None, set_memory=None, wholebody=False):
+    """qlamd_placement over torch tensors (or numpy arrays) in the memory space of the call, each checked before the library
+    reads or writes B elements behind its pointer: order / iterations / prev_iterations / next_order int32 [B].  The balance
+    step's warm start: prev_working_set / working_set int32 [B] and set_memory int32 [B, 4] (the bits of uint32 words).
+    wholebody: the whole-body step's 64-bit sets, 8 bytes per robot (int32 [B, 2] or int64 [B]), and its table int64 [B, 4],
+    which is an argument of its own there (the struct's member stays NULL); None when no array of the struct is given."""
+    for name, a in (("order", order), ("iterations", iterations), ("prev_iterations", prev_iterations), ("next_order", next_order)):
+        if a is not None and not _is(a, "int32", B):
+            raise ValueError("%s must be a contiguous int32 tensor of %d elements" % (name, B))
+    for name, a in (("prev_working_set", prev_working_set), ("working_set", working_set)):
+        if a is None:
+            continue
+        if wholebody and (a.numel() * a.element_size() != 8 * B or not a.is_contiguous()):
+            raise ValueError("%s must be a contiguous tensor of 8 bytes per robot" % name)
+        if not wholebody and not _is(a, "int32", B):
+            raise ValueError("%s must be a contiguous int32 tensor of %d elements (the 32 bits of a uint32)" % (name, B))
+    bits = "64" if wholebody else "32"
+    if set_memory is not None and not _is(set_memory, "int" + bits, 4 * B):
+        raise ValueError("set_memory must be a contiguous int%s tensor of %d x 4 elements (the %s bits of a uint%s)" % (bits, B, bits, bits))
+    arrays = (order, iterations, prev_iterations, next_order, prev_working_set, working_set)
+    if wholebody and all(a is None for a in arrays):
+        return None
+    ptrs = [_ptr(a) for a in arrays]
+    return Placement(*ptrs[:4], int(policy), *ptrs[4:], None if wholebody else _ptr(set_memory))
+
+
+def _pose_batch(problems, memory):
+    pb, keep = PoseBatch(), []
+    for key, field in POSE_FIELD_OF_KEY:
+        a = problems.get(key)
+        if a is not None and memory == MEM_HOST:
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+        setattr(pb, field, _ptr(a))
+    return pb, keep
+
+
+def _wholebody_batch(state, keep):
+    """qlamd_wholebody_batch over numpy arrays (kept alive in `keep`) or torch CUDA tensors."""
+    wb = WholebodyBatch()
+    for key, field in WHOLEBODY_FIELDS:
+        v = state.get(key)
+        if v is None:
+            continue
+        if not hasattr(v, "data_ptr"):
+            v = np.ascontiguousarray(v, dtype=np.uint8 if key == "stance" else np.float64)
+            keep.append(v)
+        setattr(wb, field, _ptr(v))
+    return wb
+
+
+def _robot_state_fields(zeros, want=None):
+    """qlamd_robot_state_fields over fresh outputs, zeros(width, dtype name) making each: -> (RobotStateFields, dict of them)."""
+    f, out = RobotStateFields(), {}
+    for name, w, dtype in [(n, w, "float64") for n, w in ROBOT_STATE_FIELDS] + [("support_leg", 4, "uint8"), ("leg_mode", 4, "uint8")]:
+        if want is None or name in want:
+            out[name] = zeros(w, dtype)
+            setattr(f, name, _ptr(out[name]))
+    return f, out
+
+
+# ---- the wrappers ------------------------------------------------------------------------------------------------------------
 def strerror(code):
     return lib().qlamd_strerror(int(code)).decode()
 
@@ -290,13 +424,40 @@ def strerror(code):
 def set_memory_slot(support_mask):
     """qlamd_set_memory_slot: the slot of qlamd_placement::set_memory [B][4] that belongs to a support mask (LF = bit 0, RF = 1,
     RH = 2, LH = 3) -- the library's own table, the one its kernels use."""
-    return int(lib().qlamd_set_memory_slot(C.c_uint(int(support_mask))))
+    return int(lib().qlamd_set_memory_slot(int(support_mask)))
+
+
+def tick_command_bytes(batch):
+    """Size of the opaque `command` block of qlamd_tick_batch (zero-filled before the first tick)."""
+    return int(lib().qlamd_tick_command_bytes(int(batch)))
 
 
 def default_params():
-    p = BalanceParams()
-    lib().qlamd_balance_default_params(C.byref(p))
-    return p
+    return _filled(BalanceParams, "qlamd_balance_default_params")
+
+
+def default_robot_model():
+    return _filled(RobotModel, "qlamd_default_robot_model")
+
+
+def default_swing_params():
+    return _filled(SwingParams, "qlamd_swing_default_params")
+
+
+def default_pose_params():
+    return _filled(PoseParams, "qlamd_pose_default_params")
+
+
+def default_ik_params():
+    return _filled(IkParams, "qlamd_ik_default_params")
+
+
+def default_joint_pid_params():
+    return _filled(JointPidParams, "qlamd_joint_pid_default_params")
+
+
+def default_wholebody_params():
+    return _filled(WholebodyParams, "qlamd_wholebody_default_params")
 
 
 def robot_params_fill(params):
@@ -307,22 +468,9 @@ def robot_params_fill(params):
         params = [params]
     arr = params if isinstance(params, C.Array) else (BalanceParams * len(params))(*params)
     out = np.zeros((len(arr), ROBOT_PARAMS_DOUBLES), dtype=np.float64)
-    rc = lib().qlamd_robot_params_fill(C.addressof(arr) if len(arr) else None, len(arr), out.ctypes.data if len(arr) else None)
-    if rc != OK and len(arr):
-        raise QlamdError(rc, "qlamd_robot_params_fill")
+    if len(arr):
+        _call(lib().qlamd_robot_params_fill, C.addressof(arr), len(arr), out.ctypes.data)
     return out
-
-
-def default_pose_params():
-    p = PoseParams()
-    lib().qlamd_pose_default_params(C.byref(p))
-    return p
-
-
-def default_robot_model():
-    m = RobotModel()
-    lib().qlamd_default_robot_model(C.byref(m))
-    return m
 
 
 class Context:
@@ -331,10 +479,8 @@ class Context:
     def __init__(self, params=None, model=None, device=0):
         self._h = C.c_void_p()
         self.params = params if params is not None else default_params()
-        rc = lib().qlamd_context_create(C.byref(self.params), C.byref(model) if model is not None else None,
-                                        int(device), C.byref(self._h))
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_context_create")
+        _call(lib().qlamd_context_create, C.byref(self.params), C.byref(model) if model is not None else None, int(device),
+              C.byref(self._h))
         self.device = device
 
     def close(self):
@@ -349,192 +495,38 @@ class Context:
             pass
 
     def set_option(self, option, value):
-        """qlamd_set_option (OPT_* / ON_FAILURE_* below)."""
-        rc = lib().qlamd_set_option(self._h, int(option), int(value))
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_set_option")
+        """qlamd_set_option (OPT_* and their values above)."""
+        _call(lib().qlamd_set_option, self._h, int(option), int(value))
 
     def counter(self, which):
-        """qlamd_get_counter (COUNTER_* below); waits for the device."""
+        """qlamd_get_counter (COUNTER_* above); waits for the device.  0 from a build that has no counters yet."""
         v = C.c_int64(0)
         if not hasattr(lib(), "qlamd_get_counter"):
             return 0
-        rc = lib().qlamd_get_counter(self._h, int(which), C.byref(v))
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_get_counter")
+        _call(lib().qlamd_get_counter, self._h, int(which), C.byref(v))
         return int(v.value)
 
     def reserve(self, max_batch):
         """Size the context's device scratch for batches up to max_batch (qlamd_reserve): before capturing the whole tick."""
-        rc = lib().qlamd_reserve(self._h, C.c_int64(int(max_batch)))
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_reserve")
+        _call(lib().qlamd_reserve, self._h, int(max_batch))
 
     def set_robots_per_wave(self, rpw):
-        rc = lib().qlamd_set_robots_per_wave(self._h, int(rpw))
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_set_robots_per_wave")
+        _call(lib().qlamd_set_robots_per_wave, self._h, int(rpw))
 
     # ---- host (numpy) buffers -------------------------------------------------
     def balance_solve_host(self, state, normals=None, want_forces=True, tau=None, grf=None):
         """tau / grf: C-contiguous float64 [B,12] arrays to write into (what QLAMD_ON_FAILURE_KEEP leaves alone is the
         caller's), fresh zeros otherwise."""
-        B = int(np.asarray(state["q"]).reshape(-1, 12).shape[0])
-        sb, keep = StateBatch(), []
-        for key, field, k in FIELD_OF_KEY:
-            a = np.ascontiguousarray(np.asarray(state[key], dtype=np.float64).reshape(B, k))
-            keep.append(a)
-            setattr(sb, field, a.ctypes.data)
-        st = np.ascontiguousarray(np.asarray(state["stance"], dtype=np.uint8).reshape(B, 4))
-        sb.support_leg = st.ctypes.data
-        if normals is not None:
-            nw = np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(B, 12))
-            keep.append(nw)
-            sb.surface_normal = nw.ctypes.data
+        sb, keep, B = _state_batch(state, normals, MEM_HOST)
         tau = _host_out(tau, B, "tau")
         grf = _host_out(grf, B, "grf") if want_forces else None
         status = np.full(B, -1, dtype=np.int32)
-        rc = lib().qlamd_balance_solve_batch(self._h, C.byref(sb), B, tau.ctypes.data,
-                                             grf.ctypes.data if want_forces else None, status.ctypes.data,
-                                             MEM_HOST, None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_balance_solve_batch")
+        _call(lib().qlamd_balance_solve_batch, self._h, C.byref(sb), B, _ptr(tau), _ptr(grf), _ptr(status), MEM_HOST, None)
         return tau, grf, status
-
-    # ---- device (torch) buffers ------------------------------------------------
-    def balance_solve_device(self, dstate, tau, grf, status, stream=None):
-        """dstate: dict of torch CUDA tensors (keys of synth.make_states, plus optional
-        'normals'); tau/grf/status: preallocated CUDA tensors.  Asynchronous."""
-        sb = StateBatch()
-        B = dstate["q"].shape[0]
-        for key, field, _ in FIELD_OF_KEY:
-            setattr(sb, field, dstate[key].data_ptr())
-        sb.support_leg = dstate["stance"].data_ptr()
-        if dstate.get("normals") is not None:
-            sb.surface_normal = dstate["normals"].data_ptr()
-        rc = lib().qlamd_balance_solve_batch(self._h, C.byref(sb), B, tau.data_ptr(),
-                                             grf.data_ptr() if grf is not None else None, status.data_ptr(),
-                                             MEM_DEVICE, C.c_void_p(stream) if stream else None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_balance_solve_batch")
-
-    def balance_solve_placed_device(self, dstate, tau, grf, status, order=None, iterations=None, prev_iterations=None,
-                                    next_order=None, policy=0, stream=None, prev_working_set=None, working_set=None,
-                                    set_memory=None):
-        """qlamd_balance_solve_placed_batch on torch CUDA tensors: order = int32 [B] permutation (slot -> robot) or None,
-        iterations = int32 [B] output or None; prev_iterations / next_order = the counts of the previous call and the
-        placement for the next one (both or neither); set_memory = int32 [B, 4], the working set per support set, updated in
-        place (instead of prev_working_set).  Asynchronous."""
-        sb = StateBatch()
-        B = dstate["q"].shape[0]
-        for key, field, _ in FIELD_OF_KEY:
-            setattr(sb, field, dstate[key].data_ptr())
-        sb.support_leg = dstate["stance"].data_ptr()
-        if dstate.get("normals") is not None:
-            sb.surface_normal = dstate["normals"].data_ptr()
-        for name, t in (("order", order), ("iterations", iterations), ("prev_iterations", prev_iterations), ("next_order", next_order)):
-            if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != B or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous int32 tensor of %d elements" % (name, B))
-        for name, t in (("prev_working_set", prev_working_set), ("working_set", working_set)):
-            if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != B or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous int32 tensor of %d elements (the 32 bits of a uint32)" % (name, B))
-        _check_set_memory(set_memory, B)
-        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
-                       _ptr(prev_working_set), _ptr(working_set), _ptr(set_memory))
-        rc = lib().qlamd_balance_solve_placed_batch(self._h, C.byref(sb), B, C.byref(pl), tau.data_ptr(),
-                                                    grf.data_ptr() if grf is not None else None, status.data_ptr(),
-                                                    MEM_DEVICE, C.c_void_p(stream) if stream else None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_balance_solve_placed_batch")
-
-    def force_distribution_placed_device(self, q, quat, support, wrench, tau, grf, status, normals=None, order=None, iterations=None,
-                                         prev_iterations=None, next_order=None, policy=0, stream=None, prev_working_set=None,
-                                         working_set=None, set_memory=None):
-        """qlamd_force_distribution_placed_batch on torch CUDA tensors (q [B, 12], quat [B, 4], support uint8 [B, 4], wrench
-        [B, 6]); the placement's arguments as balance_solve_placed_device.  Asynchronous."""
-        B = q.shape[0]
-        _check_set_memory(set_memory, B)
-        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
-                       _ptr(prev_working_set), _ptr(working_set), _ptr(set_memory))
-        rc = lib().qlamd_force_distribution_placed_batch(self._h, _ptr(q), _ptr(quat), _ptr(support), _ptr(normals), _ptr(wrench), B,
-                                                         C.byref(pl), _ptr(tau), _ptr(grf), _ptr(status), MEM_DEVICE,
-                                                         C.c_void_p(stream) if stream else None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_force_distribution_placed_batch")
-
-    def balance_solve_robot_params_device(self, dstate, robot_params, tau, grf, status, order=None, iterations=None,
-                                          prev_iterations=None, next_order=None, policy=0, stream=None, prev_working_set=None,
-                                          working_set=None, set_memory=None):
-        """qlamd_balance_solve_robot_params_batch on torch CUDA tensors: robot_params = float64 [B, 32], robot i's folded record
-        (robot_params_fill) in row i; the other arguments as balance_solve_placed_device (prev_iterations / next_order are
-        passed on for the library to refuse).  Asynchronous."""
-        sb = StateBatch()
-        B = dstate["q"].shape[0]
-        for key, field, _ in FIELD_OF_KEY:
-            setattr(sb, field, dstate[key].data_ptr())
-        sb.support_leg = dstate["stance"].data_ptr()
-        if dstate.get("normals") is not None:
-            sb.surface_normal = dstate["normals"].data_ptr()
-        if robot_params is not None and (str(robot_params.dtype) != "torch.float64" or robot_params.numel() != ROBOT_PARAMS_DOUBLES * B or
-                                         not robot_params.is_contiguous()):
-            raise ValueError("robot_params must be a contiguous float64 tensor of %d x %d elements" % (B, ROBOT_PARAMS_DOUBLES))
-        for name, t in (("order", order), ("iterations", iterations), ("prev_iterations", prev_iterations), ("next_order", next_order),
-                        ("prev_working_set", prev_working_set), ("working_set", working_set)):
-            if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != B or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous int32 tensor of %d elements" % (name, B))
-        _check_set_memory(set_memory, B)
-        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
-                       _ptr(prev_working_set), _ptr(working_set), _ptr(set_memory))
-        rc = lib().qlamd_balance_solve_robot_params_batch(self._h, C.byref(sb), _ptr(robot_params), B, C.byref(pl), tau.data_ptr(),
-                                                          grf.data_ptr() if grf is not None else None, status.data_ptr(),
-                                                          MEM_DEVICE, C.c_void_p(stream) if stream else None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_balance_solve_robot_params_batch")
-
-    def balance_solve_robot_params_host(self, state, robot_params, order=None, normals=None, want_forces=True):
-        """qlamd_balance_solve_robot_params_batch with host (numpy) buffers: robot_params float64 [B, 32] -> (tau, grf, status,
-        iterations)."""
-        B = int(np.asarray(state["q"]).reshape(-1, 12).shape[0])
-        sb, keep = StateBatch(), []
-        for key, field, k in FIELD_OF_KEY:
-            a = np.ascontiguousarray(np.asarray(state[key], dtype=np.float64).reshape(B, k))
-            keep.append(a)
-            setattr(sb, field, a.ctypes.data)
-        st = np.ascontiguousarray(np.asarray(state["stance"], dtype=np.uint8).reshape(B, 4))
-        sb.support_leg = st.ctypes.data
-        if normals is not None:
-            nw = np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(B, 12))
-            keep.append(nw)
-            sb.surface_normal = nw.ctypes.data
-        if order is not None:
-            order = np.ascontiguousarray(np.asarray(order, dtype=np.int32).reshape(B))
-        if robot_params is not None:
-            robot_params = np.ascontiguousarray(np.asarray(robot_params, dtype=np.float64).reshape(B, ROBOT_PARAMS_DOUBLES))
-        tau = np.zeros((B, 12))
-        grf = np.zeros((B, 12)) if want_forces else None
-        status = np.full(B, -1, dtype=np.int32)
-        iters = np.full(B, -1, dtype=np.int32)
-        pl = Placement(_ptr(order), iters.ctypes.data)
-        rc = lib().qlamd_balance_solve_robot_params_batch(self._h, C.byref(sb), _ptr(robot_params), B, C.byref(pl), tau.ctypes.data,
-                                                          grf.ctypes.data if want_forces else None, status.ctypes.data, MEM_HOST, None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_balance_solve_robot_params_batch")
-        return tau, grf, status, iters
 
     def balance_solve_placed_host(self, state, order=None, normals=None, want_forces=True, prev_iterations=None, policy=0):
         """qlamd_balance_solve_placed_batch with host (numpy) buffers -> (tau, grf, status, iterations[, next_order])."""
-        B = int(np.asarray(state["q"]).reshape(-1, 12).shape[0])
-        sb, keep = StateBatch(), []
-        for key, field, k in FIELD_OF_KEY:
-            a = np.ascontiguousarray(np.asarray(state[key], dtype=np.float64).reshape(B, k))
-            keep.append(a)
-            setattr(sb, field, a.ctypes.data)
-        st = np.ascontiguousarray(np.asarray(state["stance"], dtype=np.uint8).reshape(B, 4))
-        sb.support_leg = st.ctypes.data
-        if normals is not None:
-            nw = np.ascontiguousarray(np.asarray(normals, dtype=np.float64).reshape(B, 12))
-            keep.append(nw)
-            sb.surface_normal = nw.ctypes.data
+        sb, keep, B = _state_batch(state, normals, MEM_HOST)
         if order is not None:
             order = np.ascontiguousarray(np.asarray(order, dtype=np.int32).reshape(B))
         nxt = None
@@ -545,74 +537,105 @@ class Context:
         grf = np.zeros((B, 12)) if want_forces else None
         status = np.full(B, -1, dtype=np.int32)
         iters = np.full(B, -1, dtype=np.int32)
-        pl = Placement(_ptr(order), iters.ctypes.data, _ptr(prev_iterations), _ptr(nxt), int(policy))
-        rc = lib().qlamd_balance_solve_placed_batch(self._h, C.byref(sb), B, C.byref(pl), tau.ctypes.data,
-                                                    grf.ctypes.data if want_forces else None, status.ctypes.data, MEM_HOST, None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_balance_solve_placed_batch")
+        pl = _placement(B, policy, order, iters, prev_iterations, nxt)
+        _call(lib().qlamd_balance_solve_placed_batch, self._h, C.byref(sb), B, C.byref(pl), _ptr(tau), _ptr(grf), _ptr(status),
+              MEM_HOST, None)
         return (tau, grf, status, iters) if nxt is None else (tau, grf, status, iters, nxt)
+
+    def balance_solve_robot_params_host(self, state, robot_params, order=None, normals=None, want_forces=True):
+        """qlamd_balance_solve_robot_params_batch with host (numpy) buffers: robot_params float64 [B, 32] -> (tau, grf, status,
+        iterations)."""
+        sb, keep, B = _state_batch(state, normals, MEM_HOST)
+        if order is not None:
+            order = np.ascontiguousarray(np.asarray(order, dtype=np.int32).reshape(B))
+        if robot_params is not None:
+            robot_params = np.ascontiguousarray(np.asarray(robot_params, dtype=np.float64).reshape(B, ROBOT_PARAMS_DOUBLES))
+        tau = np.zeros((B, 12))
+        grf = np.zeros((B, 12)) if want_forces else None
+        status = np.full(B, -1, dtype=np.int32)
+        iters = np.full(B, -1, dtype=np.int32)
+        pl = _placement(B, 0, order, iters)
+        _call(lib().qlamd_balance_solve_robot_params_batch, self._h, C.byref(sb), _ptr(robot_params), B, C.byref(pl), _ptr(tau),
+              _ptr(grf), _ptr(status), MEM_HOST, None)
+        return tau, grf, status, iters
+
+    # ---- device (torch) buffers ------------------------------------------------
+    def balance_solve_device(self, dstate, tau, grf, status, stream=None):
+        """dstate: dict of torch CUDA tensors (keys of synth.make_states, plus optional
+        'normals'); tau/grf/status: preallocated CUDA tensors.  Asynchronous."""
+        sb, _, B = _state_batch(dstate, dstate.get("normals"), MEM_DEVICE)
+        _call(lib().qlamd_balance_solve_batch, self._h, C.byref(sb), B, tau.data_ptr(), _ptr(grf), status.data_ptr(), MEM_DEVICE,
+              _stream(stream))
+
+    def balance_solve_placed_device(self, dstate, tau, grf, status, order=None, iterations=None, prev_iterations=None,
+                                    next_order=None, policy=0, stream=None, prev_working_set=None, working_set=None,
+                                    set_memory=None):
+        """qlamd_balance_solve_placed_batch on torch CUDA tensors: order = int32 [B] permutation (slot -> robot) or None,
+        iterations = int32 [B] output or None; prev_iterations / next_order = the counts of the previous call and the
+        placement for the next one (both or neither); set_memory = int32 [B, 4], the working set per support set, updated in
+        place (instead of prev_working_set).  Asynchronous."""
+        sb, _, B = _state_batch(dstate, dstate.get("normals"), MEM_DEVICE)
+        pl = _placement(B, policy, order, iterations, prev_iterations, next_order, prev_working_set, working_set, set_memory)
+        _call(lib().qlamd_balance_solve_placed_batch, self._h, C.byref(sb), B, C.byref(pl), tau.data_ptr(), _ptr(grf),
+              status.data_ptr(), MEM_DEVICE, _stream(stream))
+
+    def force_distribution_placed_device(self, q, quat, support, wrench, tau, grf, status, normals=None, order=None, iterations=None,
+                                         prev_iterations=None, next_order=None, policy=0, stream=None, prev_working_set=None,
+                                         working_set=None, set_memory=None):
+        """qlamd_force_distribution_placed_batch on torch CUDA tensors (q [B, 12], quat [B, 4], support uint8 [B, 4], wrench
+        [B, 6]); the placement's arguments as balance_solve_placed_device.  Asynchronous."""
+        B = q.shape[0]
+        pl = _placement(B, policy, order, iterations, prev_iterations, next_order, prev_working_set, working_set, set_memory)
+        _call(lib().qlamd_force_distribution_placed_batch, self._h, _ptr(q), _ptr(quat), _ptr(support), _ptr(normals), _ptr(wrench), B,
+              C.byref(pl), _ptr(tau), _ptr(grf), _ptr(status), MEM_DEVICE, _stream(stream))
+
+    def balance_solve_robot_params_device(self, dstate, robot_params, tau, grf, status, order=None, iterations=None,
+                                          prev_iterations=None, next_order=None, policy=0, stream=None, prev_working_set=None,
+                                          working_set=None, set_memory=None):
+        """qlamd_balance_solve_robot_params_batch on torch CUDA tensors: robot_params = float64 [B, 32], robot i's folded record
+        (robot_params_fill) in row i; the other arguments as balance_solve_placed_device (prev_iterations / next_order are
+        passed on for the library to refuse).  Asynchronous."""
+        sb, _, B = _state_batch(dstate, dstate.get("normals"), MEM_DEVICE)
+        if robot_params is not None and not _is(robot_params, "float64", ROBOT_PARAMS_DOUBLES * B):
+            raise ValueError("robot_params must be a contiguous float64 tensor of %d x %d elements" % (B, ROBOT_PARAMS_DOUBLES))
+        pl = _placement(B, policy, order, iterations, prev_iterations, next_order, prev_working_set, working_set, set_memory)
+        _call(lib().qlamd_balance_solve_robot_params_batch, self._h, C.byref(sb), _ptr(robot_params), B, C.byref(pl), tau.data_ptr(),
+              _ptr(grf), status.data_ptr(), MEM_DEVICE, _stream(stream))
 
     def place_next_call(self, order=None, iterations=None, prev_iterations=None, next_order=None, policy=0):
         """qlamd_place_next_call with torch int32 CUDA tensors (or all None to withdraw a pending placement)."""
-        if order is None and iterations is None and next_order is None:
-            rc = lib().qlamd_place_next_call(self._h, None)
-        else:
-            pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy))
-            rc = lib().qlamd_place_next_call(self._h, C.byref(pl))
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_place_next_call")
+        given = [a for a in (order, iterations, next_order) if a is not None]
+        pl = _placement(given[0].numel(), policy, order, iterations, prev_iterations, next_order) if given else None
+        _call(lib().qlamd_place_next_call, self._h, C.byref(pl) if pl is not None else None)
 
     def placement_from_iterations(self, iterations, order=None, policy=0, stream=None):
         """qlamd_placement_from_iterations: numpy int32 [B] -> numpy order (synchronous), or torch int32 CUDA tensors
         (order preallocated, asynchronous on `stream`)."""
         if hasattr(iterations, "data_ptr"):
-            B = iterations.numel()
+            B, memory = iterations.numel(), MEM_DEVICE
             if order is None or str(order.dtype) != "torch.int32" or order.numel() != B or str(iterations.dtype) != "torch.int32":
                 raise ValueError("device memory: pass int32 tensors iterations and order of equal length")
-            rc = lib().qlamd_placement_from_iterations(self._h, iterations.data_ptr(), B, int(policy), order.data_ptr(),
-                                                       MEM_DEVICE, C.c_void_p(stream) if stream else None)
         else:
-            it = np.ascontiguousarray(np.asarray(iterations, dtype=np.int32).reshape(-1))
-            B = it.shape[0]
+            iterations = np.ascontiguousarray(np.asarray(iterations, dtype=np.int32).reshape(-1))
+            B, memory, stream = iterations.shape[0], MEM_HOST, None
             order = np.full(B, -1, dtype=np.int32)
-            rc = lib().qlamd_placement_from_iterations(self._h, it.ctypes.data, B, int(policy), order.ctypes.data, MEM_HOST, None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_placement_from_iterations")
+        _call(lib().qlamd_placement_from_iterations, self._h, _ptr(iterations), B, int(policy), _ptr(order), memory, _stream(stream))
         return order
 
     def virtual_wrench_device(self, dstate, wrench, stream=None):
-        sb = StateBatch()
-        for key, field, _ in FIELD_OF_KEY:
-            setattr(sb, field, dstate[key].data_ptr())
-        sb.support_leg = dstate["stance"].data_ptr()
-        rc = lib().qlamd_virtual_wrench_batch(self._h, C.byref(sb), dstate["q"].shape[0], wrench.data_ptr(),
-                                              MEM_DEVICE, C.c_void_p(stream) if stream else None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_virtual_wrench_batch")
+        sb, _, B = _state_batch(dstate, None, MEM_DEVICE)
+        _call(lib().qlamd_virtual_wrench_batch, self._h, C.byref(sb), B, wrench.data_ptr(), MEM_DEVICE, _stream(stream))
 
     def leg_kinematics_device(self, q, quat, foot=None, jac=None, grav=None, stream=None):
-        rc = lib().qlamd_leg_kinematics_batch(
-            self._h, q.data_ptr(), quat.data_ptr(), q.shape[0],
-            foot.data_ptr() if foot is not None else None, jac.data_ptr() if jac is not None else None,
-            grav.data_ptr() if grav is not None else None, MEM_DEVICE, C.c_void_p(stream) if stream else None)
-        if rc != OK:
-            raise QlamdError(rc, "qlamd_leg_kinematics_batch")
+        _call(lib().qlamd_leg_kinematics_batch, self._h, q.data_ptr(), quat.data_ptr(), q.shape[0], _ptr(foot), _ptr(jac), _ptr(grav),
+              MEM_DEVICE, _stream(stream))
 
 
 def virtual_wrench(ctx, state):
     """qlamd_virtual_wrench_batch on host buffers (state dict as synth.make_states) -> wrench [B,6]."""
-    B = int(np.asarray(state["base_pos"]).shape[0])
-    sb, keep = StateBatch(), []
-    for key, field, k in FIELD_OF_KEY:
-        if key == "q":
-            continue
-        a = np.ascontiguousarray(np.asarray(state[key], dtype=np.float64).reshape(B, k))
-        keep.append(a)
-        setattr(sb, field, a.ctypes.data)
+    sb, keep, B = _state_batch(state, None, MEM_HOST, skip=("q", "stance"))   # (the entry reads the base and desired-base fields only)
     w = np.zeros((B, 6))
-    rc = lib().qlamd_virtual_wrench_batch(ctx._h, C.byref(sb), B, w.ctypes.data, MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_virtual_wrench_batch")
+    _call(lib().qlamd_virtual_wrench_batch, ctx._h, C.byref(sb), B, w.ctypes.data, MEM_HOST, None)
     return w
 
 
@@ -621,35 +644,8 @@ def leg_kinematics(ctx, q, quat):
     q = np.ascontiguousarray(q, dtype=np.float64); quat = np.ascontiguousarray(quat, dtype=np.float64)
     B = q.shape[0]
     foot, jac, grav = np.zeros((B, 4, 3)), np.zeros((B, 4, 9)), np.zeros((B, 4, 3))
-    rc = lib().qlamd_leg_kinematics_batch(ctx._h, q.ctypes.data, quat.ctypes.data, B, foot.ctypes.data, jac.ctypes.data,
-                                          grav.ctypes.data, MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_leg_kinematics_batch")
+    _call(lib().qlamd_leg_kinematics_batch, ctx._h, _ptr(q), _ptr(quat), B, _ptr(foot), _ptr(jac), _ptr(grav), MEM_HOST, None)
     return foot, jac, grav
-
-
-def _ptr(a):
-    """data pointer of a numpy array or a torch tensor (None -> NULL)."""
-    if a is None:
-        return None
-    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
-
-
-def _check_set_memory(t, B):
-    """qlamd_placement::set_memory as a torch tensor: int32 [B, 4], contiguous (alignment is the library's to refuse)."""
-    if t is not None and (str(t.dtype) != "torch.int32" or t.numel() != 4 * B or not t.is_contiguous()):
-        raise ValueError("set_memory must be a contiguous int32 tensor of %d x 4 elements (the 32 bits of a uint32)" % B)
-
-
-def _host_out(a, B, name):
-    """A caller-supplied host output array the library writes B * 96 bytes into: float64, C-contiguous, [B, 12] -- or a
-    fresh one.  (The library cannot see a numpy array's dtype or strides: a float32 or transposed array would be
-    overrun.)"""
-    if a is None:
-        return np.zeros((B, 12))
-    if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags["C_CONTIGUOUS"] and a.shape == (B, 12)):
-        raise ValueError("%s must be a C-contiguous float64 array of shape (%d, 12)" % (name, B))
-    return a
 
 
 def force_distribution(ctx, q, quat, support, wrench, normals=None, memory=MEM_HOST, tau=None, grf=None):
@@ -663,17 +659,9 @@ def force_distribution(ctx, q, quat, support, wrench, normals=None, memory=MEM_H
     elif tau is None or grf is None:
         raise ValueError("device memory: pass preallocated tau / grf tensors")
     st = np.full(B, -1, dtype=np.int32)
-    rc = lib().qlamd_force_distribution_batch(ctx._h, _ptr(q), _ptr(quat), _ptr(support), _ptr(normals), _ptr(wrench), B,
-                                              _ptr(tau), _ptr(grf), _ptr(st), memory, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_force_distribution_batch")
+    _call(lib().qlamd_force_distribution_batch, ctx._h, _ptr(q), _ptr(quat), _ptr(support), _ptr(normals), _ptr(wrench), B, _ptr(tau),
+          _ptr(grf), _ptr(st), memory, None)
     return tau, grf, st
-
-
-def default_swing_params():
-    p = SwingParams()
-    lib().qlamd_swing_default_params(C.byref(p))
-    return p
 
 
 def swing_leg_torque(ctx, q, qd, qd_oldest, target_pos, target_vel, support, q_id=None, params=None, memory=MEM_HOST,
@@ -686,17 +674,8 @@ def swing_leg_torque(ctx, q, qd, qd_oldest, target_pos, target_vel, support, q_i
     sb = SwingBatch(*[_ptr(a) for a in arrs])
     B = int(arrs[0].shape[0])
     tau = np.zeros((B, 12)) if memory == MEM_HOST else out
-    rc = lib().qlamd_swing_leg_torque_batch(ctx._h, C.byref(prm), C.byref(sb), B, _ptr(tau), memory,
-                                            C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_swing_leg_torque_batch")
+    _call(lib().qlamd_swing_leg_torque_batch, ctx._h, C.byref(prm), C.byref(sb), B, _ptr(tau), memory, _stream(stream))
     return tau
-
-
-def default_joint_pid_params():
-    p = JointPidParams()
-    lib().qlamd_joint_pid_default_params(C.byref(p))
-    return p
 
 
 def swing_branch(ctx, joint_effort, q, qd, qd_oldest, target_pos, target_vel, support, base_orientation, joint_command,
@@ -716,10 +695,8 @@ def swing_branch(ctx, joint_effort, q, qd, qd_oldest, target_pos, target_vel, su
     sb = SwingBatch(*[_ptr(a) for a in arrs])
     ex = SwingBranchExtra(*[_ptr(a) for a in ext])
     B = int(arrs[0].shape[0])
-    rc = lib().qlamd_swing_branch_batch(ctx._h, C.byref(prm), C.byref(pidp), C.byref(sb), C.byref(ex), float(period), B,
-                                        _ptr(joint_effort), memory, C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_swing_branch_batch")
+    _call(lib().qlamd_swing_branch_batch, ctx._h, C.byref(prm), C.byref(pidp), C.byref(sb), C.byref(ex), float(period), B,
+          _ptr(joint_effort), memory, _stream(stream))
     return joint_effort
 
 
@@ -729,34 +706,13 @@ def pose_sqp(ctx, problems, params=None, memory=MEM_HOST, out=None, stream=None)
     memory; for device memory the preallocated tensors passed in `out`."""
     prm = params if params is not None else default_pose_params()
     B = int(problems["pose"].shape[0])
-    pb = PoseBatch()
-    keep = []
-    for key, field in POSE_FIELD_OF_KEY:
-        a = problems.get(key)
-        if a is not None and memory == MEM_HOST:
-            a = np.ascontiguousarray(a)
-            keep.append(a)
-        setattr(pb, field, _ptr(a))
+    pb, keep = _pose_batch(problems, memory)
     if memory == MEM_HOST:
         pose = np.zeros((B, 7)); it = np.zeros(B, dtype=np.int32); st = np.full(B, -1, dtype=np.int32)
     else:
         pose, it, st = out
-    rc = lib().qlamd_pose_sqp_batch(ctx._h, C.byref(prm), C.byref(pb), B, _ptr(pose), _ptr(it), _ptr(st), memory,
-                                    C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_pose_sqp_batch")
+    _call(lib().qlamd_pose_sqp_batch, ctx._h, C.byref(prm), C.byref(pb), B, _ptr(pose), _ptr(it), _ptr(st), memory, _stream(stream))
     return pose, it, st
-
-
-def _pose_batch(problems, memory):
-    pb, keep = PoseBatch(), []
-    for key, field in POSE_FIELD_OF_KEY:
-        a = problems.get(key)
-        if a is not None and memory == MEM_HOST:
-            a = np.ascontiguousarray(a)
-            keep.append(a)
-        setattr(pb, field, _ptr(a))
-    return pb, keep
 
 
 def pose_qp(ctx, problems, params=None):
@@ -765,9 +721,7 @@ def pose_qp(ctx, problems, params=None):
     B = int(problems["pose"].shape[0])
     pb, keep = _pose_batch(problems, MEM_HOST)
     pose = np.zeros((B, 7)); st = np.full(B, -1, dtype=np.int32)
-    rc = lib().qlamd_pose_qp_batch(ctx._h, C.byref(prm), C.byref(pb), B, _ptr(pose), _ptr(st), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_pose_qp_batch")
+    _call(lib().qlamd_pose_qp_batch, ctx._h, C.byref(prm), C.byref(pb), B, _ptr(pose), _ptr(st), MEM_HOST, None)
     return pose, st
 
 
@@ -778,9 +732,7 @@ def pose_check(ctx, problems, min_len=None, leg_tol=0.0, params=None):
     pb, keep = _pose_batch(problems, MEM_HOST)
     mn = None if min_len is None else np.ascontiguousarray(min_len, dtype=np.float64)
     ok = np.zeros(B, dtype=np.uint8)
-    rc = lib().qlamd_pose_check_batch(ctx._h, C.byref(prm), C.byref(pb), _ptr(mn), float(leg_tol), B, _ptr(ok), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_pose_check_batch")
+    _call(lib().qlamd_pose_check_batch, ctx._h, C.byref(prm), C.byref(pb), _ptr(mn), float(leg_tol), B, _ptr(ok), MEM_HOST, None)
     return ok
 
 
@@ -791,9 +743,7 @@ def pose_geometric(ctx, problems, stance_for_orientation=None, params=None):
     pb, keep = _pose_batch(problems, MEM_HOST)
     sfo = None if stance_for_orientation is None else np.ascontiguousarray(stance_for_orientation, dtype=np.float64)
     pose = np.zeros((B, 7))
-    rc = lib().qlamd_pose_geometric_batch(ctx._h, C.byref(prm), C.byref(pb), _ptr(sfo), B, _ptr(pose), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_pose_geometric_batch")
+    _call(lib().qlamd_pose_geometric_batch, ctx._h, C.byref(prm), C.byref(pb), _ptr(sfo), B, _ptr(pose), MEM_HOST, None)
     return pose
 
 
@@ -811,11 +761,8 @@ def base_auto_optimize_pose(ctx, problems, stance_for_orientation=None, min_len=
     else:
         sfo, mn = stance_for_orientation, min_len
         pose, stage, it, st = out
-    rc = lib().qlamd_base_auto_optimize_pose_batch(ctx._h, C.byref(prm), C.byref(pb), _ptr(sfo), _ptr(mn), float(leg_tol), B,
-                                                   _ptr(pose), _ptr(stage), _ptr(it), _ptr(st), memory,
-                                                   C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_base_auto_optimize_pose_batch")
+    _call(lib().qlamd_base_auto_optimize_pose_batch, ctx._h, C.byref(prm), C.byref(pb), _ptr(sfo), _ptr(mn), float(leg_tol), B,
+          _ptr(pose), _ptr(stage), _ptr(it), _ptr(st), memory, _stream(stream))
     return pose, stage, it, st
 
 
@@ -830,10 +777,7 @@ def leg_state_machine(ctx, io, index_quirk=1, memory=MEM_HOST, stream=None):
             assert a.dtype == dt and a.flags["C_CONTIGUOUS"], name
         setattr(b, name, _ptr(a))
     B = int(io["phase"].shape[0])
-    rc = lib().qlamd_leg_state_machine_batch(ctx._h, C.byref(b), int(index_quirk), B, memory,
-                                             C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_leg_state_machine_batch")
+    _call(lib().qlamd_leg_state_machine_batch, ctx._h, C.byref(b), int(index_quirk), B, memory, _stream(stream))
     return io
 
 
@@ -843,21 +787,11 @@ def robot_state_unpack(ctx, messages, offsets, want=None):
     buf = np.frombuffer(messages, dtype=np.uint8) if isinstance(messages, (bytes, bytearray)) else np.ascontiguousarray(messages, np.uint8)
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     B = off.shape[0] - 1
-    f, out = RobotStateFields(), {}
-    for name, w in ROBOT_STATE_FIELDS:
-        if want is None or name in want:
-            out[name] = np.zeros((B, w))
-            setattr(f, name, _ptr(out[name]))
-    for name in ("support_leg", "leg_mode"):
-        if want is None or name in want:
-            out[name] = np.zeros((B, 4), np.uint8)
-            setattr(f, name, _ptr(out[name]))
+    f, out = _robot_state_fields(lambda w, dtype: np.zeros((B, w), dtype), want)
     st = np.full(B, -1, np.int32)
     if buf.size == 0:
         buf = np.zeros(1, np.uint8)
-    rc = lib().qlamd_robot_state_unpack_batch(ctx._h, _ptr(buf), _ptr(off), B, C.byref(f), _ptr(st), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_robot_state_unpack_batch")
+    _call(lib().qlamd_robot_state_unpack_batch, ctx._h, _ptr(buf), _ptr(off), B, C.byref(f), _ptr(st), MEM_HOST, None)
     return out, st
 
 
@@ -866,25 +800,11 @@ def robot_state_unpack_device(ctx, messages, offsets, stream=None):
     (dict of CUDA tensors, status tensor).  Asynchronous."""
     import torch
     B = offsets.numel() - 1
-    f, out = RobotStateFields(), {}
-    for name, w in ROBOT_STATE_FIELDS:
-        out[name] = torch.zeros(B, w, dtype=torch.float64, device=messages.device)
-        setattr(f, name, out[name].data_ptr())
-    for name in ("support_leg", "leg_mode"):
-        out[name] = torch.zeros(B, 4, dtype=torch.uint8, device=messages.device)
-        setattr(f, name, out[name].data_ptr())
+    f, out = _robot_state_fields(lambda w, dtype: torch.zeros(B, w, dtype=getattr(torch, dtype), device=messages.device))
     st = torch.full((B,), -1, dtype=torch.int32, device=messages.device)
-    rc = lib().qlamd_robot_state_unpack_batch(ctx._h, messages.data_ptr(), offsets.data_ptr(), B, C.byref(f), st.data_ptr(), MEM_DEVICE,
-                                              C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_robot_state_unpack_batch")
+    _call(lib().qlamd_robot_state_unpack_batch, ctx._h, messages.data_ptr(), offsets.data_ptr(), B, C.byref(f), st.data_ptr(),
+          MEM_DEVICE, _stream(stream))
     return out, st
-
-
-def default_ik_params():
-    p = IkParams()
-    lib().qlamd_ik_default_params(C.byref(p))
-    return p
 
 
 def leg_inverse_kinematics(ctx, foot_position, joint_position_last=None, params=None):
@@ -894,9 +814,7 @@ def leg_inverse_kinematics(ctx, foot_position, joint_position_last=None, params=
     last = None if joint_position_last is None else np.ascontiguousarray(joint_position_last, dtype=np.float64)
     B = foot.shape[0]
     q = np.zeros((B, 12)); ok = np.zeros((B, 4), np.uint8)
-    rc = lib().qlamd_leg_inverse_kinematics_batch(ctx._h, C.byref(prm), _ptr(foot), _ptr(last), B, _ptr(q), _ptr(ok), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_leg_inverse_kinematics_batch")
+    _call(lib().qlamd_leg_inverse_kinematics_batch, ctx._h, C.byref(prm), _ptr(foot), _ptr(last), B, _ptr(q), _ptr(ok), MEM_HOST, None)
     return q, ok
 
 
@@ -912,14 +830,9 @@ def qp_solve(ctx, G, g0, CE, ce0, CI, ci0):
     CI = None if m == 0 else np.ascontiguousarray(CI, dtype=np.float64)
     ci0 = None if m == 0 else np.ascontiguousarray(ci0, dtype=np.float64)
     x = np.zeros((B, n)); f = np.zeros(B); st = np.full(B, -1, dtype=np.int32)
-    rc = lib().qlamd_qp_solve_batch(ctx._h, n, p, m, _ptr(G), _ptr(g0), _ptr(CE), _ptr(ce0), _ptr(CI), _ptr(ci0), B,
-                                    _ptr(x), _ptr(f), _ptr(st), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_qp_solve_batch")
+    _call(lib().qlamd_qp_solve_batch, ctx._h, n, p, m, _ptr(G), _ptr(g0), _ptr(CE), _ptr(ce0), _ptr(CI), _ptr(ci0), B, _ptr(x), _ptr(f),
+          _ptr(st), MEM_HOST, None)
     return x, f, st
-
-
-NO_BOUND = 1.7976931348623157e308   # std::numeric_limits<double>::max(): what the reference writes for "no bound"
 
 
 def weighted_lsq_qp(ctx, A, S, b, W, Ceq=None, ceq=None, D=None, d=None, f=None, memory=MEM_HOST, out=None, stream=None):
@@ -939,10 +852,7 @@ def weighted_lsq_qp(ctx, A, S, b, W, Ceq=None, ceq=None, D=None, d=None, f=None,
         if out is None:
             raise ValueError("device memory: pass out=(x [B,n] float64, status [B] int32) as preallocated CUDA tensors")
         x, st = out
-    rc = lib().qlamd_weighted_lsq_qp_batch(ctx._h, n, k, p, m, *[_ptr(a) for a in arrs], B, _ptr(x), _ptr(st), memory,
-                                           C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_weighted_lsq_qp_batch")
+    _call(lib().qlamd_weighted_lsq_qp_batch, ctx._h, n, k, p, m, *[_ptr(a) for a in arrs], B, _ptr(x), _ptr(st), memory, _stream(stream))
     return x, st
 
 
@@ -973,26 +883,6 @@ def to_device_records(state, device="cuda:0"):
     return out
 
 
-def default_wholebody_params():
-    p = WholebodyParams()
-    lib().qlamd_wholebody_default_params(C.byref(p))
-    return p
-
-
-def _wholebody_batch(state, keep):
-    """qlamd_wholebody_batch over numpy arrays (kept alive in `keep`) or torch CUDA tensors."""
-    wb = WholebodyBatch()
-    for key, field in WHOLEBODY_FIELDS:
-        v = state.get(key)
-        if v is None:
-            continue
-        if not hasattr(v, "data_ptr"):
-            v = np.ascontiguousarray(v, dtype=np.uint8 if key == "stance" else np.float64)
-            keep.append(v)
-        setattr(wb, field, _ptr(v))
-    return wb
-
-
 def wholebody_dynamics(ctx, state, gravity=9.81, want=("M", "h", "Jc")):
     """qlamd_wholebody_dynamics_batch on host buffers -> dict with M [B,18,18], h [B,18], Jc [B,12,18]."""
     keep = []
@@ -1000,11 +890,15 @@ def wholebody_dynamics(ctx, state, gravity=9.81, want=("M", "h", "Jc")):
     B = state["q"].shape[0]
     out = dict(M=np.zeros((B, 18, 18)) if "M" in want else None, h=np.zeros((B, 18)) if "h" in want else None,
                Jc=np.zeros((B, 12, 18)) if "Jc" in want else None)
-    rc = lib().qlamd_wholebody_dynamics_batch(ctx._h, C.byref(wb), C.c_double(gravity), B, _ptr(out["M"]), _ptr(out["h"]),
-                                              _ptr(out["Jc"]), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_wholebody_dynamics_batch")
+    _call(lib().qlamd_wholebody_dynamics_batch, ctx._h, C.byref(wb), float(gravity), B, _ptr(out["M"]), _ptr(out["h"]), _ptr(out["Jc"]),
+          MEM_HOST, None)
     return out
+
+
+def wholebody_dynamics_device(ctx, dstate, M, h, Jc, gravity=9.81, stream=None):
+    wb = _wholebody_batch(dstate, [])
+    _call(lib().qlamd_wholebody_dynamics_batch, ctx._h, C.byref(wb), float(gravity), dstate["q"].shape[0], _ptr(M), _ptr(h), _ptr(Jc),
+          MEM_DEVICE, _stream(stream))
 
 
 def wholebody_solve(ctx, state, params=None, tau=None, grf=None):
@@ -1015,9 +909,7 @@ def wholebody_solve(ctx, state, params=None, tau=None, grf=None):
     B = state["q"].shape[0]
     tau, grf = _host_out(tau, B, "tau"), _host_out(grf, B, "grf")
     st = np.full(B, -1, np.int32)
-    rc = lib().qlamd_wholebody_solve_batch(ctx._h, C.byref(prm), C.byref(wb), B, _ptr(tau), _ptr(grf), _ptr(st), MEM_HOST, None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_wholebody_solve_batch")
+    _call(lib().qlamd_wholebody_solve_batch, ctx._h, C.byref(prm), C.byref(wb), B, _ptr(tau), _ptr(grf), _ptr(st), MEM_HOST, None)
     return tau, grf, st
 
 
@@ -1025,11 +917,8 @@ def wholebody_solve_device(ctx, dstate, tau, grf, status, params=None, stream=No
     """Same entry on torch CUDA tensors (dstate: dict from to_device); asynchronous."""
     prm = params if params is not None else default_wholebody_params()
     wb = _wholebody_batch(dstate, [])
-    rc = lib().qlamd_wholebody_solve_batch(ctx._h, C.byref(prm), C.byref(wb), dstate["q"].shape[0], tau.data_ptr(),
-                                           grf.data_ptr() if grf is not None else None, status.data_ptr(), MEM_DEVICE,
-                                           C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_wholebody_solve_batch")
+    _call(lib().qlamd_wholebody_solve_batch, ctx._h, C.byref(prm), C.byref(wb), dstate["q"].shape[0], tau.data_ptr(), _ptr(grf),
+          status.data_ptr(), MEM_DEVICE, _stream(stream))
 
 
 def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, stream=None, order=None, iterations=None,
@@ -1041,44 +930,14 @@ def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, st
     prm = params if params is not None else default_wholebody_params()
     wb = _wholebody_batch(dstate, [])
     B = dstate["q"].shape[0]
-    if set_memory is not None and (str(set_memory.dtype) != "torch.int64" or set_memory.numel() != 4 * B or not set_memory.is_contiguous()):
-        raise ValueError("set_memory must be a contiguous int64 tensor of %d x 4 elements (the 64 bits of a uint64)" % B)
-    for name, t in (("prev_working_set", prev_working_set), ("working_set", working_set)):
-        if t is not None and (t.numel() * t.element_size() != 8 * B or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous tensor of 8 bytes per robot" % name)
-    pl = None
-    if any(t is not None for t in (order, iterations, prev_iterations, next_order, prev_working_set, working_set)):
-        pl = Placement(_ptr(order), _ptr(iterations), _ptr(prev_iterations), _ptr(next_order), int(policy),
-                       _ptr(prev_working_set), _ptr(working_set), None)
-    fn = lib().qlamd_wholebody_solve_placed_batch
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                   C.c_int, C.c_void_p]
-    rc = fn(ctx._h, C.addressof(prm), C.addressof(wb), B, C.addressof(pl) if pl is not None else None, _ptr(set_memory),
-            tau.data_ptr(), grf.data_ptr() if grf is not None else None, status.data_ptr(), MEM_DEVICE,
-            C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_wholebody_solve_placed_batch")
-
-
-class PlantNext(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("joint_position", "joint_velocity", "base_position", "base_orientation",
-                                           "base_linear_velocity", "base_angular_velocity")]
-
-
-# field of qlamd_plant_next -> (key of the state dict, elements per robot)
-PLANT_NEXT_FIELDS = (("joint_position", "q", 12), ("joint_velocity", "qd", 12), ("base_position", "base_pos", 3),
-                     ("base_orientation", "base_quat", 4), ("base_linear_velocity", "base_linvel", 3),
-                     ("base_angular_velocity", "base_angvel", 3))
+    pl = _placement(B, policy, order, iterations, prev_iterations, next_order, prev_working_set, working_set, set_memory, wholebody=True)
+    _call(lib().qlamd_wholebody_solve_placed_batch, ctx._h, C.byref(prm), C.byref(wb), B, C.byref(pl) if pl is not None else None,
+          _ptr(set_memory), tau.data_ptr(), _ptr(grf), status.data_ptr(), MEM_DEVICE, _stream(stream))
 
 
 def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream):
-    fn = lib().qlamd_wholebody_forward_dynamics_batch
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_void_p,
-                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    rc = fn(ctx._h, C.addressof(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B, _ptr(acc), _ptr(f),
-            C.addressof(nxt) if nxt is not None else None, _ptr(status), memory, C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_wholebody_forward_dynamics_batch")
+    _call(lib().qlamd_wholebody_forward_dynamics_batch, ctx._h, C.byref(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B,
+          _ptr(acc), _ptr(f), C.byref(nxt) if nxt is not None else None, _ptr(status), memory, _stream(stream))
 
 
 def wholebody_forward_dynamics(ctx, state, tau, g_ext=None, gravity=9.81, dt=None, free_flight=False, in_place=False):
@@ -1122,37 +981,6 @@ def wholebody_forward_dynamics_device(ctx, dstate, tau, status, acc=None, f=None
                 float(dt), acc, f, nxt, status, MEM_DEVICE, stream)
 
 
-def wholebody_dynamics_device(ctx, dstate, M, h, Jc, gravity=9.81, stream=None):
-    wb = _wholebody_batch(dstate, [])
-    rc = lib().qlamd_wholebody_dynamics_batch(ctx._h, C.byref(wb), C.c_double(gravity), dstate["q"].shape[0],
-                                              M.data_ptr() if M is not None else None, h.data_ptr() if h is not None else None,
-                                              Jc.data_ptr() if Jc is not None else None, MEM_DEVICE,
-                                              C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_wholebody_dynamics_batch")
-
-
-OPT_ON_FAILURE, OPT_REFINE_PASSES, OPT_DYNAMICS_FORM, OPT_PLACEMENT_WAIT, OPT_WARM_FALLBACK, OPT_STATE_LAYOUT = 1, 2, 5, 6, 7, 8
-STATE_FIELDS, STATE_RECORDS, STATE_RECORD_DOUBLES = 0, 1, 48
-# offsets (doubles) of the fields inside a qlamd_state_record (include/qlamd.h), by the keys of synth.make_states
-STATE_RECORD_OFFSETS = {"q": 0, "base_pos": 12, "base_quat": 16, "base_linvel": 20, "base_angvel": 23, "des_pos": 26, "des_quat": 30,
-                        "des_linvel": 34, "des_angvel": 37}
-COUNTER_PLACEMENT_GIVE_UPS, COUNTER_WARM_RETRIES = 0, 1
-DYNAMICS_AUTO, DYNAMICS_LEG, DYNAMICS_ROW = 0, 1, 2
-ON_FAILURE_ZERO, ON_FAILURE_KEEP = 0, 1
-PLACEMENT_AUTO, PLACEMENT_LATENCY, PLACEMENT_THROUGHPUT, PLACEMENT_NONE = 0, 1, 2, 3
-STATUS_NO_COMMAND = 4
-STATUS_DEPENDENT_EQUALITY = 5
-
-
-def tick_command_bytes(batch):
-    """Size of the opaque `command` block of qlamd_tick_batch (zero-filled before the first tick)."""
-    fn = lib().qlamd_tick_command_bytes
-    fn.restype = C.c_size_t
-    fn.argtypes = [C.c_int64]
-    return int(fn(int(batch)))
-
-
 def full_tick(ctx, io, period, index_quirk=1, params=None, pid=None, memory=MEM_HOST, stream=None):
     """qlamd_full_tick_batch.  `io`: dict with the fields of qlamd_tick_batch (TICK_FIELDS: C-contiguous numpy arrays of
     those dtypes for host memory, torch CUDA tensors for device memory; `leg_state_code` and `command` may be None);
@@ -1176,8 +1004,6 @@ def full_tick(ctx, io, period, index_quirk=1, params=None, pid=None, memory=MEM_
             raise ValueError("set_memory must hold %d x 4 words of 32 bits" % B)
         if hasattr(sm, "is_contiguous") and not sm.is_contiguous():
             raise ValueError("set_memory must be contiguous")
-    rc = lib().qlamd_full_tick_batch(ctx._h, C.byref(prm), C.byref(pidp), C.byref(tb), float(period), int(index_quirk), B, memory,
-                                     C.c_void_p(stream) if stream else None)
-    if rc != OK:
-        raise QlamdError(rc, "qlamd_full_tick_batch")
+    _call(lib().qlamd_full_tick_batch, ctx._h, C.byref(prm), C.byref(pidp), C.byref(tb), float(period), int(index_quirk), B, memory,
+          _stream(stream))
     return io

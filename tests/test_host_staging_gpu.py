@@ -41,10 +41,7 @@ def test_balance_and_force_distribution(gpu, B, forces):
     tau, grf, st = ctx.balance_solve_host(s, want_forces=forces)
     d = capi.to_device(s)
     dt, dg, ds = dev(torch, np.zeros((B, 12))), dev(torch, np.zeros((B, 12))), dev(torch, np.zeros(B, np.int32))
-    sb = capi.StateBatch()
-    for key, field, _ in capi.FIELD_OF_KEY:
-        setattr(sb, field, d[key].data_ptr())
-    sb.support_leg = d["stance"].data_ptr()
+    sb, _, _ = capi._state_batch(d, None, capi.MEM_DEVICE)
     assert capi.lib().qlamd_balance_solve_batch(ctx._h, C.byref(sb), B, dt.data_ptr(), dg.data_ptr() if forces else None,
                                                 ds.data_ptr(), capi.MEM_DEVICE, None) == capi.OK
     same(tau, dt, torch); same(st, ds, torch)

@@ -228,10 +228,7 @@ def test_next_placement_made_inside_the_solve_equals_the_placement_entry(gpu, B)
         assert np.array_equal(out[4], ctx.placement_from_iterations(prev, policy=capi.PLACEMENT_LATENCY))
         assert np.array_equal(out[0], t0)
         pl = capi.Placement(None, None, d_prev.data_ptr(), None, 0)
-        sb = capi.StateBatch()
-        for key, field, _ in capi.FIELD_OF_KEY:
-            setattr(sb, field, d[key].data_ptr())
-        sb.support_leg = d["stance"].data_ptr()
+        sb, _, _ = capi._state_batch(d, None, capi.MEM_DEVICE)
         tau = torch.zeros(B, 12, dtype=torch.float64, device="cuda:0")
         status = torch.zeros(B, dtype=torch.int32, device="cuda:0")
         rc = capi.lib().qlamd_balance_solve_placed_batch(ctx._h, C.byref(sb), B, C.byref(pl), tau.data_ptr(), None, status.data_ptr(),

@@ -355,13 +355,7 @@ def test_refusals(gpu):
     assert np.array_equal(mem.cpu().numpy().view(np.uint32), mark) and np.array_equal(big.cpu().numpy().view(np.uint32)[1:], mark.reshape(-1))
 
     # host memory: as any warm start
-    sb, keep = capi.StateBatch(), []
-    for key, field, k in capi.FIELD_OF_KEY:
-        a = np.ascontiguousarray(np.asarray(s[key], dtype=np.float64).reshape(B, k))
-        keep.append(a)
-        setattr(sb, field, a.ctypes.data)
-    st = np.ascontiguousarray(s["stance"], dtype=np.uint8)
-    sb.support_leg = st.ctypes.data
+    sb, keep, _ = capi._state_batch(s, None, capi.MEM_HOST)
     host_mem = np.zeros((B + 4, 4), dtype=np.uint32)
     host_mem = host_mem.reshape(-1)[(-host_mem.ctypes.data // 4) % 4:][:4 * B]   # (16-byte aligned: refused for being host memory)
     assert host_mem.ctypes.data % 16 == 0

@@ -159,13 +159,7 @@ def test_warm_start_arguments(gpu):
     torch.cuda.synchronize()
     assert torch.equal(ws, ws2) and (status == 0).all()
     # host memory: refused (a host-buffer call is bound by its copies)
-    sb, keep = capi.StateBatch(), []
-    for key, field, k in capi.FIELD_OF_KEY:
-        a = np.ascontiguousarray(s[key], dtype=np.float64).reshape(B, k)
-        keep.append(a)
-        setattr(sb, field, a.ctypes.data)
-    st8 = np.ascontiguousarray(s["stance"], dtype=np.uint8)
-    sb.support_leg = st8.ctypes.data
+    sb, keep, _ = capi._state_batch(s, None, capi.MEM_HOST)
     h_tau, h_st, h_ws = np.zeros((B, 12)), np.zeros(B, np.int32), np.zeros(B, np.uint32)
     pl = capi.Placement(None, None, None, None, 0, None, h_ws.ctypes.data)
     rc = capi.lib().qlamd_balance_solve_placed_batch(ctx._h, C.byref(sb), B, C.byref(pl), h_tau.ctypes.data, None, h_st.ctypes.data,
