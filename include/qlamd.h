@@ -841,7 +841,8 @@ int qlamd_wholebody_solve_placed_batch(qlamd_context *ctx, const qlamd_wholebody
  * gamma: the classical acceleration of each flagged foot point at nu' = 0, base coordinates --
  * w x v + w x (w x r) + 2 w x (J_leg qd) + J_leg' qd (J_leg' the time derivative) -- so that the flagged feet have zero
  * acceleration in the world.  The contacts are HARD constraints on the flagged feet: no contact detection, no friction
- * limit, no drift stabilisation -- f may pull.  No leg flagged, or in->support_leg NULL: free flight, f = 0 and
+ * limit, no drift stabilisation -- f may pull (qlamd_wholebody_plant_step_batch of qlamd_plant_contacts.h adds the touchdown
+ * impact, a velocity term against the drift and a report of pulling and sliding feet).  No leg flagged, or in->support_leg NULL: free flight, f = 0 and
  * nu' = M^-1 (...).  in->desired_* and in->surface_normal are ignored.
  *   joint_effort      [B][12]          tau
  *   generalized_force [B][18] or NULL  g_ext, in the order of nu (added to the right-hand side as it is)
@@ -876,6 +877,9 @@ int qlamd_wholebody_forward_dynamics_batch(qlamd_context *ctx, const qlamd_whole
         const double *base_position /*[B][3], needed only with next*/, double gravity, double dt,
         int64_t batch, double *acceleration /*[B][18] or NULL*/, double *contact_force /*[B][12] or NULL*/,
         const qlamd_plant_next *next /*or NULL*/, int32_t *status, int memory, void *stream);
+
+/* The plant step with touchdown impacts, contact stabilisation and a contact report -- what a closed loop calls -- is declared
+ * in qlamd_plant_contacts.h, which this header includes at its end. */
 
 /* ---- the whole control tick in one call (SURVEY.md section 8 row a1 with rows f1 and f2) -----------------------
  * What the plugin does between one /desired_robot_state message and 12 effort commands:
@@ -968,4 +972,9 @@ int qlamd_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* the plant step with contacts (QLAMD_HAS_PLANT_CONTACTS, qlamd_wholebody_plant_step_batch): part of this interface, kept in a
+ * file of its own that ships beside this one -- including qlamd.h is enough */
+#include "qlamd_plant_contacts.h"
+
 #endif /* QLAMD_H */

@@ -935,15 +935,20 @@ def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, st
           _ptr(set_memory), tau.data_ptr(), _ptr(grf), status.data_ptr(), MEM_DEVICE, _stream(stream))
 
 
-def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream):
-    _call(lib().qlamd_wholebody_forward_dynamics_batch, ctx._h, C.byref(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B,
-          _ptr(acc), _ptr(f), C.byref(nxt) if nxt is not None else None, _ptr(status), memory, _stream(stream))
+def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream, contacts=None):
+    """contacts: None = qlamd_wholebody_forward_dynamics_batch; (entry, struct or None) = that entry -- plant_contacts.py's declared
+    qlamd_wholebody_plant_step_batch -- with the struct (None: NULL) in front of `status`."""
+    head = (ctx._h, C.byref(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B, _ptr(acc), _ptr(f),
+            C.byref(nxt) if nxt is not None else None)
+    if contacts is None:
+        _call(lib().qlamd_wholebody_forward_dynamics_batch, *head, _ptr(status), memory, _stream(stream))
+    else:
+        entry, struct = contacts
+        _call(entry, *head, C.byref(struct) if struct is not None else None, _ptr(status), memory, _stream(stream))
 
 
-def wholebody_forward_dynamics(ctx, state, tau, g_ext=None, gravity=9.81, dt=None, free_flight=False, in_place=False):
-    """qlamd_wholebody_forward_dynamics_batch on host buffers -> dict with acc [B,18], f [B,12], status [B] and, with dt, `next`:
-    the state after dt under the keys of `state` (q, qd, base_pos, base_quat, base_linvel, base_angvel).  state["stance"] flags the
-    held feet (free_flight: support_leg = NULL); in_place: the next state is written over `state`'s own arrays."""
+def _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, contacts=None, extra=None):
+    """The host form of both plant entries (contacts as _plant_call's) -> dict with acc, f, status, `next` with dt, and `extra`."""
     keep = []
     B = state["q"].shape[0]
     if in_place:
@@ -959,26 +964,39 @@ def wholebody_forward_dynamics(ctx, state, tau, g_ext=None, gravity=9.81, dt=Non
     if tau.shape != (B, 12) or (g_ext is not None and g_ext.shape != (B, 18)):
         raise ValueError("tau must be [%d, 12] and g_ext [%d, 18]" % (B, B))
     out = dict(acc=np.zeros((B, 18)), f=np.zeros((B, 12)), status=np.full(B, -1, np.int32))
+    out.update(extra or {})
     nxt, pos = None, None
     if dt is not None:
         pos = np.ascontiguousarray(state["base_pos"], dtype=np.float64)
         out["next"] = {key: (state[key] if in_place else np.zeros((B, n))) for _, key, n in PLANT_NEXT_FIELDS}
         nxt = PlantNext(*[_ptr(out["next"][key]) for _, key, _ in PLANT_NEXT_FIELDS])
     _plant_call(ctx, wb, B, tau, g_ext, pos, float(gravity), float(dt) if dt is not None else 0.0, out["acc"], out["f"], nxt,
-                out["status"], MEM_HOST, None)
+                out["status"], MEM_HOST, None, contacts)
     return out
+
+
+def wholebody_forward_dynamics(ctx, state, tau, g_ext=None, gravity=9.81, dt=None, free_flight=False, in_place=False):
+    """qlamd_wholebody_forward_dynamics_batch on host buffers -> dict with acc [B,18], f [B,12], status [B] and, with dt, `next`:
+    the state after dt under the keys of `state` (q, qd, base_pos, base_quat, base_linvel, base_angvel).  state["stance"] flags the
+    held feet (free_flight: support_leg = NULL); in_place: the next state is written over `state`'s own arrays."""
+    return _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place)
+
+
+def _plant_device(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream, contacts=None):
+    """The device form of both plant entries (contacts as _plant_call's)."""
+    wb = _wholebody_batch(dstate, [])
+    if free_flight:
+        wb.support_leg = None
+    nxt = None if next is None else PlantNext(*[_ptr(next[key]) for _, key, _ in PLANT_NEXT_FIELDS])
+    _plant_call(ctx, wb, dstate["q"].shape[0], tau, g_ext, dstate.get("base_pos") if next is not None else None, float(gravity),
+                float(dt), acc, f, nxt, status, MEM_DEVICE, stream, contacts)
 
 
 def wholebody_forward_dynamics_device(ctx, dstate, tau, status, acc=None, f=None, g_ext=None, gravity=9.81, dt=0.0, next=None,
                                       free_flight=False, stream=None):
     """Same entry on torch CUDA tensors; asynchronous.  next: dict of tensors under the state's keys (q, qd, base_pos, base_quat,
     base_linvel, base_angvel) or NULL; it may be `dstate` itself, which then needs "base_pos" (a rollout in place)."""
-    wb = _wholebody_batch(dstate, [])
-    if free_flight:
-        wb.support_leg = None
-    nxt = None if next is None else PlantNext(*[_ptr(next[key]) for _, key, _ in PLANT_NEXT_FIELDS])
-    _plant_call(ctx, wb, dstate["q"].shape[0], tau, g_ext, dstate.get("base_pos") if next is not None else None, float(gravity),
-                float(dt), acc, f, nxt, status, MEM_DEVICE, stream)
+    _plant_device(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream)
 
 
 def full_tick(ctx, io, period, index_quirk=1, params=None, pid=None, memory=MEM_HOST, stream=None):

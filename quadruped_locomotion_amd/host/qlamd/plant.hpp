@@ -1,7 +1,9 @@
 // The plant step from C++: the state of a batch of robots on the host and qlamd_wholebody_forward_dynamics_batch on it, in
 // place -- what a simulation loop calls after the controller (balance_controller/WholeBodyController.hpp gives the efforts of
 // one robot, qlamd_wholebody_solve_batch those of a batch).  The contacts are hard constraints on the flagged feet: no contact
-// detection, no friction limit, no drift stabilisation (include/qlamd.h).  Needs qlamd.h only.
+// detection, no friction limit, no drift stabilisation (include/qlamd.h) -- for forward_dynamics() and step().  With a
+// qlamd.h that has qlamd_wholebody_plant_step_batch (QLAMD_HAS_PLANT_CONTACTS), step_with_contacts() is the step for a closed loop: a plastic impact at
+// every touchdown, a velocity term that keeps held feet at rest, and a report of pulling and sliding feet.  Needs qlamd.h only.
 #pragma once
 
 #include <cstdint>
@@ -23,6 +25,9 @@ struct PlantState {
         base_orientation((size_t)batch * 4), base_linear_velocity((size_t)batch * 3), base_angular_velocity((size_t)batch * 3),
         support_leg((size_t)batch * 4) {
     for (int64_t i = 0; i < batch; i++) base_orientation[(size_t)i * 4] = 1.0;
+#ifdef QLAMD_HAS_PLANT_CONTACTS
+    previous_support_leg.assign((size_t)batch * 4, 0);
+#endif
   }
   int64_t size() const { return (int64_t)(joint_position.size() / 12); }
   // the state as the input of any whole-body entry (desired_* and surface_normal stay NULL: the plant step ignores them)
@@ -41,6 +46,10 @@ struct PlantState {
   std::vector<double> base_orientation;                        // [B][4] (w, x, y, z)
   std::vector<double> base_linear_velocity, base_angular_velocity; // [B][3] world / base
   std::vector<uint8_t> support_leg;                            // [B][4] the feet held by the contact constraints
+#ifdef QLAMD_HAS_PLANT_CONTACTS
+  std::vector<uint8_t> previous_support_leg;                   // [B][4] support_leg of the step before (step_with_contacts keeps
+                                                               // it; zeros at the start: the first step projects every held foot)
+#endif
 };
 
 // nu' [B][18] and f [B][12] for the efforts joint_effort [B][12] (either output may be NULL); the library's return code
@@ -65,6 +74,34 @@ inline int step(qlamd_context *ctx, PlantState &s, const double *joint_effort, d
   return qlamd_wholebody_forward_dynamics_batch(ctx, &in, joint_effort, generalized_force, s.base_position.data(), gravity, dt, s.size(),
                                                 nullptr, contact_force, &next, status, QLAMD_MEM_HOST, nullptr);
 }
+
+#ifdef QLAMD_HAS_PLANT_CONTACTS
+// One step of `dt` in place with contacts (qlamd_wholebody_plant_step_batch): the impact over the held feet of every robot one of
+// whose feet is flagged now and was not in the step before, the dynamics at nu+ with the velocity term k_v (1/s; 1/dt brings a held
+// foot to rest within the step), the state update from nu+.  contact_force [B][12] and contact_report [B][4] (QLAMD_CONTACT_* bits
+// for the friction coefficient `friction`) or NULL.  After a call that returns QLAMD_OK the state remembers this step's flags.
+inline int step_with_contacts(qlamd_context *ctx, PlantState &s, const double *joint_effort, double gravity, double dt, double k_v,
+                              int32_t *status, double *contact_force = nullptr, uint8_t *contact_report = nullptr,
+                              double friction = 0.0, const double *generalized_force = nullptr) {
+  const qlamd_wholebody_batch in = s.batch();
+  qlamd_plant_next next;
+  next.joint_position = s.joint_position.data();
+  next.joint_velocity = s.joint_velocity.data();
+  next.base_position = s.base_position.data();
+  next.base_orientation = s.base_orientation.data();
+  next.base_linear_velocity = s.base_linear_velocity.data();
+  next.base_angular_velocity = s.base_angular_velocity.data();
+  qlamd_plant_contacts contacts{};
+  contacts.previous_support_leg = s.previous_support_leg.data();
+  contacts.velocity_gain = k_v;
+  contacts.friction_coefficient = friction;
+  contacts.contact_report = contact_report;
+  const int rc = qlamd_wholebody_plant_step_batch(ctx, &in, joint_effort, generalized_force, s.base_position.data(), gravity, dt,
+                                                  s.size(), nullptr, contact_force, &next, &contacts, status, QLAMD_MEM_HOST, nullptr);
+  if (rc == QLAMD_OK) s.previous_support_leg = s.support_leg;
+  return rc;
+}
+#endif
 
 } // namespace host
 } // namespace qlamd

@@ -12,7 +12,13 @@
    stays as drawn.  Reported: us per tick, status counts of both entries per tick range, and the fraction of robots whose final
    working set is the previous tick's (`working_set_unchanged`; 0.975 on the open-loop trajectory of bench.py).
 
-usage: closed_loop_probe.py [--batch 4096] [--ticks 64] [--batches 4096,65536,1048576] [--steps 64] [--repeats 5] [--out file]"""
+   Also per tick range: the largest and the median world speed of the held feet after the tick (Jc nu of the state the tick left).
+3. --contacts: the plant step of both parts is qlamd_wholebody_plant_step_batch.  Part 1 adds its launch with contacts == NULL
+   (the old entry's kernel), with contacts and no touchdown, and with every robot projecting; part 2 gives every tick the flags
+   of the tick before as previous_support_leg (zeros at the first tick) and --velocity-gain as k_v (1/s; default 0).
+
+usage: closed_loop_probe.py [--batch 4096] [--ticks 64] [--batches 4096,65536,1048576] [--steps 64] [--repeats 5] [--out file]
+                            [--contacts] [--velocity-gain K]"""
 import argparse
 import os
 import sys
@@ -32,9 +38,11 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--contacts", action="store_true")
+    ap.add_argument("--velocity-gain", type=float, default=0.0)
     a = ap.parse_args()
     import torch
-    from quadruped_locomotion_amd import capi, synth
+    from quadruped_locomotion_amd import capi, plant_contacts, synth
     ctx = capi.Context(device=0)
     stream = torch.cuda.current_stream().cuda_stream
     dev = dict(device="cuda:0")
@@ -72,6 +80,15 @@ def main():
         t_acc = sample(lambda: capi.wholebody_forward_dynamics_device(ctx, d, tau, st, acc=acc, f=f, stream=stream), n)
         t_step = sample(lambda: capi.wholebody_forward_dynamics_device(ctx, d, tau, st, acc=acc, f=f, dt=DT, next=nxt, stream=stream), n)
         ok = int((st == 0).sum())
+        if a.contacts:
+            zeros = torch.zeros(B, 4, dtype=torch.uint8, **dev)
+            kw = dict(acc=acc, f=f, dt=DT, next=nxt, stream=stream)
+            t_null = sample(lambda: plant_contacts.wholebody_plant_step_device(ctx, d, tau, st, contacts=False, **kw), n)
+            t_quiet = sample(lambda: plant_contacts.wholebody_plant_step_device(ctx, d, tau, st, velocity_gain=a.velocity_gain, **kw), n)
+            t_proj = sample(lambda: plant_contacts.wholebody_plant_step_device(ctx, d, tau, st, prev_stance=zeros, velocity_gain=a.velocity_gain, **kw), n)
+            say("%8d robots: qlamd_wholebody_plant_step_batch, nu', f and next state: contacts NULL %8.2f (%.2f)   contacts, no touchdown "
+                "%8.2f (%.2f)   every robot projecting %8.2f (%.2f)   status OK %d / %d"
+                % (B, t_null[0], t_null[1], t_quiet[0], t_quiet[1], t_proj[0], t_proj[1], int((st == 0).sum()), B))
         del nxt
         M, h, Jc = f64(B, 18, 18), f64(B, 18), f64(B, 12, 18)
         t_dyn = sample(lambda: capi.wholebody_dynamics_device(ctx, d, M, h, Jc, stream=stream), n)
@@ -88,6 +105,19 @@ def main():
     stance = torch.from_numpy(np.stack([synth.trot_stance(phase + k * DT / (synth.T_SWING + synth.T_STANCE)) for k in range(K)]).astype(np.uint8)).to("cuda:0")
     switched = float((stance[1:] != stance[:-1]).any(dim=2).float().mean())
 
+    def held_foot_speeds(d, flags):
+        """world speeds of the feet flagged in `flags` [B, 4]: |Jc nu| by foot (a rotation away from the world's)"""
+        Jc = f64(B, 12, 18)
+        capi.wholebody_dynamics_device(ctx, d, None, None, Jc, stream=stream)
+        w, x, y, z = d["base_quat"].unbind(1)
+        R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                         2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(B, 3, 3)
+        nu = torch.cat([torch.einsum("bji,bj->bi", R, d["base_linvel"]), d["base_angvel"], d["qd"]], dim=1)
+        speed = torch.einsum("brk,bk->br", Jc, nu).reshape(B, 4, 3).norm(dim=2)
+        return speed[flags != 0]
+
+    zero_flags = torch.zeros(B, 4, dtype=torch.uint8, **dev)
+
     def loop(timed):
         d = capi.to_device(s)
         tau, st_qp, st_pl = f64(B, 12), torch.zeros(B, dtype=torch.int32, **dev), torch.zeros(B, dtype=torch.int32, **dev)
@@ -98,7 +128,11 @@ def main():
         def tick(k):
             d["stance"] = stance[k]
             capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
-            capi.wholebody_forward_dynamics_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream)
+            if a.contacts:
+                plant_contacts.wholebody_plant_step_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream, velocity_gain=a.velocity_gain,
+                                                 prev_stance=stance[k - 1] if k else zero_flags)
+            else:
+                capi.wholebody_forward_dynamics_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream)
 
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -114,21 +148,28 @@ def main():
             torch.cuda.synchronize()
             same = float((ws == prev_ws).float().mean()) if k else float("nan")
             prev_ws.copy_(ws)
-            stats.append((int((st_qp == 0).sum()), int((st_pl == 0).sum()), same, bool(torch.isfinite(d["q"]).all())))
+            speed = held_foot_speeds(d, stance[k])
+            speed = speed[torch.isfinite(speed)]
+            stats.append((int((st_qp == 0).sum()), int((st_pl == 0).sum()), same, bool(torch.isfinite(d["q"]).all()),
+                          float(speed.max()), float(speed.median())))
         return stats
 
     stats = loop(False)
     t = [loop(True) for _ in range(a.repeats + 1)][1:]
-    say("closed loop: %d trot robots, %d ticks of qlamd_wholebody_solve_placed_batch (table) -> plant step in place, dt %.4f s; "
-        "support set switched per tick %.4f" % (B, K, DT, switched))
+    say("closed loop: %d trot robots, %d ticks of qlamd_wholebody_solve_placed_batch (table) -> plant step in place (%s), dt %.4f s; "
+        "support set switched per tick %.4f"
+        % (B, K, "with contacts, k_v = %g / s" % a.velocity_gain if a.contacts else "qlamd_wholebody_forward_dynamics_batch", DT, switched))
     say("  us per tick (two launches): %s median %.2f spread %.2f" % (" ".join("%.2f" % x for x in t), float(np.median(t)), max(t) - min(t)))
     q = max(1, K // 4)
     for lo in range(0, K, q):
         part = stats[lo:lo + q]
         same = [p[2] for p in part if p[2] == p[2]]
-        say("  ticks %3d-%3d: whole-body step OK %.4f, plant step OK %.4f, working_set_unchanged %.4f, state finite %s"
+        say("  ticks %3d-%3d: whole-body step OK %.4f, plant step OK %.4f, working_set_unchanged %.4f, state finite %s, "
+            "held-foot speed m/s: largest %.4g, median of the ticks' medians %.4g"
             % (lo, lo + len(part) - 1, np.mean([p[0] for p in part]) / B, np.mean([p[1] for p in part]) / B, float(np.mean(same)),
-               all(p[3] for p in part)))
+               all(p[3] for p in part), max(p[4] for p in part), float(np.median([p[5] for p in part]))))
+    say("  held-foot speed per tick, largest: " + " ".join("%.3g" % p[4] for p in stats))
+    say("  held-foot speed per tick, median:  " + " ".join("%.3g" % p[5] for p in stats))
     same = [p[2] for p in stats if p[2] == p[2]]
     say("  all ticks: working_set_unchanged %.4f under the closed loop (open loop, bench.py's trajectory: 0.975); warm retries %d"
         % (float(np.mean(same)), ctx.counter(capi.COUNTER_WARM_RETRIES)))
