@@ -475,14 +475,15 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
       }
       wm = sane ? wm : (mask_t)0;
     }
-    // Which form: by rounds when some robot of the wavefront brings many rows (a round of four rows is 0.95 us whatever it
-    // holds, a row on its own 0.40 us: the static bench batch -- 8 rows on average, up to 12 -- 15.5 -> 14.85 us by rounds, its
+    // Which form: by rounds when some robot of the wavefront brings many rows (a round of four rows is 1.05 us whatever it
+    // holds -- three rounds and the drop check 3.16 us at the median, profiles/r13/install_rounds.txt -- a row on its own 0.40 us:
+    // the static bench batch -- 8 rows on average, up to 12 -- 15.5 -> 14.85 us by rounds, its
     // trot batches -- one to three rows on two legs -- 22.2 -> 23.2 us: profiles/r6/ab_install_forms.txt), row by row otherwise
     // and always in the throughput form of the kernels (!kRounds).  Wavefront-uniform: one scalar branch.
     // A robot WITHOUT a set -- its first step, or one whose support legs have just changed: the robots a launch of a trot waits
     // for -- builds one by rounds as well (kGreedy): in every round each leg takes its most violated row at the current x, the
     // round installs them as equalities, up to three rounds; negative multipliers are dropped below and the method of the
-    // reference runs from there as after any warm start (same guarantees, same final check).  Four rows a round at 0.95 us
+    // reference runs from there as after any warm start (same guarantees, same final check).  Four rows a round at 1.05 us
     // instead of one a pass at 0.65 us: a robot entering double support 9.5 passes -> three rounds and the passes that remain.
 #ifdef QLAMD_NO_GREEDY
     constexpr bool kGreedy = false;   // (A/B builds)
@@ -500,13 +501,29 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
     if (by_rounds) {
       // Installed a ROUND at a time: the next row of every leg together.  Every row touches the variables of one leg, so the
       // directions of up to four rows -- z_m = H n_m, r_m = N* n_m -- are ONE broadcast sweep (column j of H and N* goes to the
-      // accumulators of leg j / 3: 24 broadcast-FMAs for all of them, what a single row used to take), and the rows then go in one
-      // after the other inside a straight block: d_k = n_k'z_k from a quad sum, the full step onto row k, the rank-one update, and the
-      // directions of the legs still to come corrected by one broadcast-FMA each (z_m -= z_k (n_m'z_k) / d_k: the quad sum that gave
-      // d_k on leg k's lanes gave n_m'z_k on leg m's) instead of being swept again.  A lone wavefront pays for dependent chains:
+      // accumulators of leg j / 3: 24 broadcast-FMAs for all of them, what a single row used to take), and the round's rows then go
+      // in as ONE block elimination, in leg order:
+      //   1. the Gram block D[m][k] = n_m'z_k: a multiply and a quad sum per k, independent of one another; D is symmetric (H is),
+      //      its 10 distinct entries go to every lane of the robot by row broadcasts;
+      //   2. D = L diag(d) L' in registers, the same on every lane.  The pivot d_k = n_k'z~_k is what the row-after-row form finds
+      //      after correcting z_k by the rows before it, so the rule that leaves a dependent row out (d_k <= 1e-6) is that form's;
+      //      a row left out, or a leg without a row, has 1 / d_k := 0, and with it its column of L, its step and its update are
+      //      exact zeros.  The steps t_k come from the slacks, eliminated with the same L;
+      //   3. the directions corrected in place, z~_k = z_k - sum_{j<k} L[k][j] z~_j, and r~_k the same way with -1 on the lane of
+      //      the slot a row has just taken (its entry of N* is + z~'/d): plain FMAs, L is on every lane.  x, u and the slots are
+      //      stepped row by row as before -- the same values in the same slot order;
+      //   4. the four rank-one updates of H and N* as one stream of 4 x 24 broadcast-FMAs with nothing between them.
+      // Row after row (the form this replaces, kept for kTorque below) the round was one chain: the pivot of row k + 1 waited for
+      // the correction by row k, that for row k's reciprocal, that for row k's quad sum, four times, with the 96 update FMAs between
+      // the links.  The same rows in the same order: equal in exact arithmetic, different in rounding only
+      // (tests/test_install_rounds_cpu.py is the arithmetic in numpy, either form).  Measured on the static bench batch, whose
+      // wavefronts take three rounds: installs + drops 3.32 -> 3.16 us at the median and a step 0.15-0.25 us shorter
+      // (profiles/r13/install_rounds.txt).  A lone wavefront pays for dependent chains and for every instruction:
       // round 5 installed a row in 0.40 us (LDS fetch of the normal -> sweep -> two row sums -> reciprocal -> update, 960 cycles:
-      // profiles/r6/warm_install_probe.txt), twelve rows in 4.8 us; a round of four is 0.7 us and three rounds are the most there are.
+      // profiles/r6/warm_install_probe.txt), twelve rows in 4.8 us; three rounds are the most there are.
       // A leg without a row in a round rides along with a zero normal and divisors biased to 1, like a ghost row of the loop.
+      // kTorque (the whole-body step) keeps the rows of a round one after the other: its kernels are at 249 registers with
+      // 428 bytes of scratch and stay instruction for instruction what they were.
       unsigned mine = (unsigned)((wm >> (kKinds * leg)) & kLegRows); // the rows of my leg still to install (lanes of a leg agree)
       const bool any_greedy = kGreedy && __builtin_amdgcn_ballot_w64(greedy) != 0ull; // (scalar)
       // (the loop in two copies -- wavefronts with a robot that builds its set, and the others, whose rounds stay the straight
@@ -580,6 +597,77 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
           fmac_bc<lane_of(j), j == 0>(za[j / 3], npj, H[j]);
           fmac_bc<lane_of(j)>(ra[j / 3], npj, Ns[j]);
         });
+        if constexpr (!kTorque) {
+          // ---- the block form: Gram block, its LDL' on every lane, corrected directions in place, one stream of updates
+          double qs[kLegs];              // on the lanes of leg m: D[m][k] = n_m'z_k
+          static_for<kLegs>([&](auto K) { constexpr int k = K; qs[k] = quad_sum(npj * za[k]); });
+          double D[kLegs][kLegs];        // D[m][k], m <= k (D is symmetric: H is), on every lane of the robot
+          double sk[kLegs];              // slack of leg k's row, on every lane
+          static_for<kLegs>([&](auto K) {
+            constexpr int k = K;
+            static_for<k + 1>([&](auto M) { constexpr int m = M; D[m][k] = bc<4 * m>(qs[k]); });
+            sk[k] = bc<4 * k>(sl);
+          });
+          // W[m][k] = n_m'z~_k (m > k) = L[m][k] d_k; a row left out has zi = 0: its column of L and its step are exact zeros
+          double W[kLegs][kLegs], L[kLegs][kLegs], zi[kLegs], tw[kLegs];
+          static_for<kLegs>([&](auto K) {
+            constexpr int k = K;
+            const int kk = (int)((kinds >> (4 * k)) & 15u) - 1; // leg k's row of this round (-1: none)
+            double dk = D[k][k], s = sk[k];
+            static_for<k>([&](auto J) {
+              constexpr int j = J;
+              dk = fma(-L[k][j], W[k][j], dk);
+              s = fma(tw[j], W[k][j], s);
+            });
+            // a row that depends on the rows installed before it (this round's earlier ones included) is left out: z'n_p is then
+            // rounding noise, which with the entries of H reaching 1 / w_reg = 1e4 means up to 1e-10, while an independent row has
+            // z'n_p >= |n|^2 / trace(G) ~ 1e-3
+            const bool ok = kk >= 0 && dk > 1e-6;
+            const double okf = sel(ok, 1.0, 0.0);
+            zi[k] = rcp_nr1(sel(ok, dk, 1.0)) * okf;            // 1 / d_k, or 0
+            tw[k] = -s * zi[k];
+            static_for<kLegs - 1 - k>([&](auto Mq) {
+              constexpr int m = k + 1 + Mq;
+              double w = D[k][m];
+              static_for<k>([&](auto J) { constexpr int j = J; w = fma(-L[k][j], W[m][j], w); });
+              W[m][k] = w;
+              L[m][k] = w * zi[k];
+            });
+            // z~_k = z_k - sum_{j<k} L[k][j] z~_j, r~_k likewise (the slot a row j < k took holds -1 there: + L[k][j] on its lane)
+            static_for<k>([&](auto J) {
+              constexpr int j = J;
+              za[k] = fma(-L[k][j], za[j], za[k]);
+              ra[k] = fma(-L[k][j], ra[j], ra[k]);
+            });
+            za[k] *= okf;
+            const double rr = ra[k] * okf;
+            x = fma(tw[k], za[k], x);
+            u = fma(-tw[k], rr, u);
+            const int newlane = __ffs(~used & 0xFFFu) - 1;
+            const bool newslot = ok && lr == newlane;
+            const int pk = kKinds * k + kk;
+            ra[k] = sel(newslot, -1.0, rr);
+            u = sel(newslot, tw[k], u);
+            idk = newslot ? pk : idk;
+            used |= ok ? (1u << newlane) : 0u;
+            act_mask |= ok ? (one << pk) : 0;
+            rnorm2 = vmax(rnorm2, dk); // (a row left out has d_k <= 1e-6 < R_norm^2)
+            q += ok ? 1 : 0;
+          });
+          // the four rank-one updates, H -= z~_k z~_k' / d_k and N* -= r~_k z~_k' / d_k, as one stream: nothing between them
+          static_for<kLegs>([&](auto K) {
+            constexpr int k = K;
+            const double nvk = za[k] * -zi[k];
+            static_for<kV>([&](auto J) {
+              constexpr int j = J;
+              fmac_bc<lane_of(j), j == 0>(H[j], nvk, za[k]);
+              fmac_bc<lane_of(j)>(Ns[j], nvk, ra[k]);
+            });
+          });
+        } else
+        // ---- kTorque: the rows of the round one after the other -- d_k = n_k'z_k from a quad sum, the full step onto row k, the
+        // rank-one update, and the directions of the legs still to come corrected by one broadcast-FMA each (z_m -= z_k (n_m'z_k) / d_k:
+        // the quad sum that gave d_k on leg k's lanes gave n_m'z_k on leg m's)
         static_for<kLegs>([&](auto K) {
           constexpr int k = K;
           // (a lone wavefront pays per instruction, and a round is four of these: everything a leg without a row, or with a row
