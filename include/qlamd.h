@@ -842,7 +842,8 @@ int qlamd_wholebody_solve_placed_batch(qlamd_context *ctx, const qlamd_wholebody
  * w x v + w x (w x r) + 2 w x (J_leg qd) + J_leg' qd (J_leg' the time derivative) -- so that the flagged feet have zero
  * acceleration in the world.  The contacts are HARD constraints on the flagged feet: no contact detection, no friction
  * limit, no drift stabilisation -- f may pull (qlamd_wholebody_plant_step_batch of qlamd_plant_contacts.h adds the touchdown
- * impact, a velocity term against the drift and a report of pulling and sliding feet).  No leg flagged, or in->support_leg NULL: free flight, f = 0 and
+ * impact, a velocity term against the drift and a report of pulling and sliding feet; qlamd_wholebody_contact_update_batch of
+ * qlamd_contact_detection.h decides which feet to flag for the next step: the detection is an entry of its own, not this one's).  No leg flagged, or in->support_leg NULL: free flight, f = 0 and
  * nu' = M^-1 (...).  in->desired_* and in->surface_normal are ignored.
  *   joint_effort      [B][12]          tau
  *   generalized_force [B][18] or NULL  g_ext, in the order of nu (added to the right-hand side as it is)
@@ -976,5 +977,7 @@ int qlamd_version(void);
 /* the plant step with contacts (QLAMD_HAS_PLANT_CONTACTS, qlamd_wholebody_plant_step_batch): part of this interface, kept in a
  * file of its own that ships beside this one -- including qlamd.h is enough */
 #include "qlamd_plant_contacts.h"
+/* ground contact detection for the plant (QLAMD_HAS_CONTACT_DETECTION, qlamd_wholebody_contact_update_batch): likewise */
+#include "qlamd_contact_detection.h"
 
 #endif /* QLAMD_H */

@@ -3,7 +3,8 @@
 // one robot, qlamd_wholebody_solve_batch those of a batch).  The contacts are hard constraints on the flagged feet: no contact
 // detection, no friction limit, no drift stabilisation (include/qlamd.h) -- for forward_dynamics() and step().  With a
 // qlamd.h that has qlamd_wholebody_plant_step_batch (QLAMD_HAS_PLANT_CONTACTS), step_with_contacts() is the step for a closed loop: a plastic impact at
-// every touchdown, a velocity term that keeps held feet at rest, and a report of pulling and sliding feet.  Needs qlamd.h only.
+// every touchdown, a velocity term that keeps held feet at rest, and a report of pulling and sliding feet; which feet
+// to flag for the next step is detect_contacts()'s to say (qlamd/contact_detection.hpp).  Needs qlamd.h only.
 #pragma once
 
 #include <cstdint>

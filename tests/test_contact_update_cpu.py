@@ -1,0 +1,381 @@
+"""The contact update (qlamd_wholebody_contact_update_batch), everything that needs no GPU: the numpy reference the GPU tests
+compare against (tests/contact_update_reference.py) checked on its own, the export, the binding against its header and the
+compiler, the header's feature-test macro and structs, the C++ wrapper, the marshalling of the Python wrappers, and the new
+kernel's resources against DESIGN.md section 4.6e."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import contact_update_reference as CUR  # noqa: E402
+import plant_reference as PR  # noqa: E402
+
+HEADER = os.path.join(ROOT, "include", "qlamd_contact_detection.h")
+GCC = ["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include")]
+
+
+# ---- the reference on its own -------------------------------------------------------------------------------------------------
+
+def test_foot_velocity_is_the_derivative_of_foot_position(oracle):
+    """u = v_W + R (w x r + J qd) against the central difference of p = pos + R r along the motion (q + t qd, the base turned by
+    exp(t w) and moved by t v_W).  Step 1e-5: the difference's error is O(eps^2 x third derivative) ~ 1e-10 x a few tens, its
+    rounding ~ 1e-16 / 1e-5; bound 1e-7."""
+    s = PR.case_states("trot", 16)[0]
+    eps, worst, fastest = 1e-5, 0.0, 0.0
+    for i in range(16):
+        def at(t):
+            quat = PR.quat_mul(s["base_quat"][i], PR.quat_exp(t * s["base_angvel"][i]))
+            return CUR.foot_world_position(s["q"][i] + t * s["qd"][i], quat / np.linalg.norm(quat), s["base_pos"][i] + t * s["base_linvel"][i])
+        u = CUR.feet(s, i)[1]
+        worst = max(worst, np.abs((at(eps) - at(-eps)) / (2.0 * eps) - u).max())
+        fastest = max(fastest, np.abs(u).max())
+    print("foot velocity against the difference of foot positions: %.3e (foot speeds up to %.3f m/s)" % (worst, fastest))
+    assert worst < 1e-7 and fastest > 0.1
+
+
+def affine_field(a, b, c, origin=(-1.0, -1.0), resolution=0.05, n=41):
+    """heights z = a x + b y + c sampled on an n x n grid"""
+    x = origin[0] + resolution * np.arange(n)
+    y = origin[1] + resolution * np.arange(n)
+    return dict(origin=origin, resolution=resolution, heights=np.ascontiguousarray(a * x[None, :] + b * y[:, None] + c))
+
+
+def test_an_affine_height_field_is_the_plane(oracle):
+    """z = a x + b y + c is the plane (-a, -b, 1) . p = c: every bilinear patch of its samples is that plane, so gap and normal of
+    the two modes agree to 1e-12 for feet inside the grid (and the flags follow)."""
+    s = PR.case_states("static", 16)[0]
+    a, b, c = 0.2, -0.15, 0.03
+    hf = affine_field(a, b, c)
+    plane = np.tile(np.array([-a, -b, 1.0, c]), (16, 1))
+    rule = dict(touchdown_distance=0.0, liftoff_distance=0.02, sensor_distance=0.0, approach_speed=0.1)
+    one, two = CUR.update_batch(s, hf=hf, **rule), CUR.update_batch(s, plane=plane, **rule)
+    assert np.abs(one["foot_pos"][:, :, :2]).max() < 0.95          # inside the grid
+    assert np.abs(one["gap"] - two["gap"]).max() < 1e-12 and np.abs(one["normals"] - two["normals"]).max() < 1e-12
+    both = one["compare"] & two["compare"]
+    assert both.sum() >= 60 and np.array_equal(one["support_next"][both], two["support_next"][both])
+    assert 8 <= one["support_next"].sum() <= 56                     # the thresholds cut through the cases
+    # outside the grid the clamp holds the border cell's patch at the border: a foot beyond x = 1 sees the height at x = 1
+    n, gap, _, _ = CUR.heightfield_terrain(hf, np.array([1.5, 0.0, 1.0]))
+    assert abs(gap - n[2] * (1.0 - (a * 1.0 + c))) < 1e-12
+
+
+def test_truth_table_of_the_flag_rule():
+    rule = dict(CUR.RULE, touchdown_distance=0.01, approach_speed=0.05, liftoff_distance=0.03, sensor_distance=0.02, release_mask=1)
+    T, P, G = CUR.TOUCHDOWN, CUR.RELEASED_PULL, CUR.RELEASED_GAP
+    #        flagged report gap     n.u     next   events sensor
+    table = [(False, 0,     0.005,  0.0,    True,  T,     True),     # near and not leaving: picked up (a foot at rest too)
+             (False, 0,     0.005,  0.05,   True,  T,     True),     # both thresholds are inclusive
+             (False, 0,     0.01,   -1.0,   True,  T,     True),
+             (False, 0,     0.005,  0.06,   False, 0,     True),     # near but moving away: left alone (a foot just released)
+             (False, 0,     0.015,  -1.0,   False, 0,     True),     # approaching but not there yet; the sensor is geometric
+             (False, 1,     0.005,  0.0,    True,  T,     True),     # the report of an unflagged leg is not read
+             (True,  0,     0.025,  1.0,    True,  0,     False),    # flagged: the hysteresis band keeps it, whatever its velocity
+             (True,  0,     0.03,   0.0,    True,  0,     False),    # released only beyond the liftoff distance
+             (True,  0,     0.031,  0.0,    False, G,     False),
+             (True,  1,     0.0,    0.0,    False, P,     True),     # it pulled
+             (True,  3,     0.04,   0.0,    False, P | G, False),    # both
+             (True,  2,     0.0,    0.0,    True,  0,     True),     # OUTSIDE_CONE is not in this release mask
+             (True,  6,     -0.01,  -1.0,   True,  0,     True)]
+    for flagged, report, gap, nu, nxt, events, sensor in table:
+        got = CUR.flag_rule(flagged, report, gap, nu, rule)
+        on_a_threshold = gap == 0.02 or (gap == 0.03 if flagged else (gap == 0.01 or nu == 0.05))
+        assert got == (nxt, events, sensor, on_a_threshold), (flagged, report, gap, nu, got)
+    assert CUR.flag_rule(True, 2, 0.0, 0.0, dict(rule, release_mask=3))[:2] == (False, P)
+    assert CUR.flag_rule(True, 1, 0.0, 0.0, dict(rule, release_mask=0))[:2] == (True, 0)
+    # borderline: within 1e-9 of a threshold that the leg's answer depends on
+    assert CUR.flag_rule(False, 0, 0.01 + 5e-10, 0.0, rule)[3] and CUR.flag_rule(False, 0, 0.0, 0.05 - 5e-10, rule)[3]
+    assert CUR.flag_rule(True, 0, 0.03 - 5e-10, 0.0, rule)[3] and CUR.flag_rule(True, 0, 0.02 + 5e-10, 0.0, rule)[3]
+    assert not CUR.flag_rule(True, 0, 0.01, 0.05, rule)[3]             # a flagged leg does not test the touchdown thresholds
+
+
+def test_the_loop_of_the_reference_has_touchdowns_and_releases(oracle):
+    """The case of tests/test_contact_update_gpu.py's loop test, on the CPU alone: 16 trot robots, 32 ticks, no foot flagged at the
+    start, the ground 5 mm under each robot's lowest foot."""
+    s, tau, plane, kw = CUR.loop_case()
+    _, ticks = CUR.loop(s, tau, CUR.LOOP_TICKS, CUR.LOOP_DT, 1.0 / CUR.LOOP_DT, CUR.LOOP_MU, plane, **kw)
+    valid = np.stack([k["valid"] for k in ticks])
+    events = np.stack([k["events"] for k in ticks])
+    touchdowns = int(((events & CUR.TOUCHDOWN) != 0)[valid].sum())
+    releases = int(((events & (CUR.RELEASED_PULL | CUR.RELEASED_GAP)) != 0)[valid].sum())
+    print("loop: %d touchdowns, %d releases, %d of %d robot-ticks dropped" % (touchdowns, releases, (~valid).sum(), valid.size))
+    assert touchdowns >= 10 and releases >= 10 and (~valid).sum() <= 0.02 * valid.size
+    assert not ticks[0]["flags"].any()
+
+
+# ---- the export, the header, the binding ------------------------------------------------------------------------------------------
+
+def test_the_library_exports_the_entries():
+    from quadruped_locomotion_amd import build, contact_detection
+    lib = build.build()
+    names = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    for name in ("qlamd_contact_update_default", "qlamd_wholebody_contact_update_batch"):
+        assert re.search(r" T %s$" % name, names, re.M), name
+    assert contact_detection.EXPORTS == ("qlamd_contact_update_default", "qlamd_wholebody_contact_update_batch")
+    assert "contact_update_kernel.hip" in build.SOURCE_NAMES
+    assert HEADER in build.headers()                                    # an edit of the header rebuilds the library
+    assert os.path.join(ROOT, "quadruped_locomotion_amd", "csrc", "contact_update_core.hpp") in build.headers()
+
+
+MIRRORS = (("qlamd_heightfield", "Heightfield", 40), ("qlamd_contact_update", "ContactUpdate", 120))
+CONSTANTS = ("CONTACT_EVENT_TOUCHDOWN", "CONTACT_EVENT_RELEASED_PULL", "CONTACT_EVENT_RELEASED_GAP")
+
+
+def test_the_binding_matches_the_header_and_the_compiler(tmp_path):
+    """What tests/test_capi_cpu.py holds capi.py to, for contact_detection.py and its header: exactly two functions, each with its
+    row in SIGNATURES (arity, the kind of each parameter, the return kind); the struct set; the mirrors have the compiler's sizes
+    and offsets; the constants have the header's values; the loaded library carries the declarations."""
+    from quadruped_locomotion_amd import build, contact_detection as CD
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    decls = re.findall(r"^(int|void) ?(qlamd_\w+)\(([^;{]*)\);", text, flags=re.M)
+    assert [name for _, name, _ in decls] == list(CD.EXPORTS) and len(decls) == 2
+    kinds_of = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double}
+    for ret, name, params in decls:
+        restype, argtypes = CD.SIGNATURES[name]
+        assert restype is {"int": C.c_int, "void": None}[ret]
+        kinds = ["pointer" if "*" in prm else " ".join(prm.split()[:-1]) for prm in (x.strip() for x in params.split(","))]
+        assert len(kinds) == len(argtypes) == {"qlamd_contact_update_default": 1, "qlamd_wholebody_contact_update_batch": 8}[name]
+        for i, (ctype, kind) in enumerate(zip(argtypes, kinds)):
+            assert ctype is (C.c_void_p if kind == "pointer" else kinds_of[kind]), (name, i, kind)
+    assert set(re.findall(r"^typedef struct (qlamd_\w+) \{", open(HEADER).read(), flags=re.M)) == {m[0] for m in MIRRORS}
+    lines = []
+    for cname, pyname, _ in MIRRORS:
+        lines.append('printf("sizeof.%s %%zu 0\\n", sizeof(%s));' % (cname, cname))
+        for member, _ in getattr(CD, pyname)._fields_:
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, member, cname, member, cname, member))
+    for n in CONSTANTS:
+        lines.append('printf("%s %%d 0\\n", QLAMD_%s);' % (n, n))
+    (tmp_path / "layout.c").write_text('#include <stddef.h>\n#include <stdio.h>\n#include "qlamd_contact_detection.h"\nint main(void) {\n  %s\n  return 0;\n}\n'
+                                       % "\n  ".join(lines))
+    subprocess.check_call(GCC + [str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")])
+    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True, timeout=60).stdout.split("\n")
+    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out if l}
+    for cname, pyname, size in MIRRORS:
+        mirror = getattr(CD, pyname)
+        assert got["sizeof." + cname][0] == C.sizeof(mirror) == size, cname
+        for member, ctype in mirror._fields_:
+            assert got[cname + "." + member] == (getattr(mirror, member).offset, C.sizeof(ctype)), (cname, member)
+    for n in CONSTANTS:
+        assert got[n][0] == getattr(CD, n)
+    build.build()
+    for name, (restype, argtypes) in CD.SIGNATURES.items():
+        fn = getattr(CD.lib(), name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes
+
+
+def test_the_header_defines_the_feature_test_macro_and_qlamd_h_includes_it(tmp_path):
+    src = tmp_path / "detection.c"
+    src.write_text('#include <stddef.h>\n#include "qlamd.h"\n'
+                   "#if !defined(QLAMD_HAS_CONTACT_DETECTION) || QLAMD_HAS_CONTACT_DETECTION != 1\n#error no contact detection\n#endif\n"
+                   "#if !defined(QLAMD_HAS_PLANT_CONTACTS)\n#error no plant contacts\n#endif\n"
+                   "#if QLAMD_CONTACT_EVENT_TOUCHDOWN != 1 || QLAMD_CONTACT_EVENT_RELEASED_PULL != 2 || QLAMD_CONTACT_EVENT_RELEASED_GAP != 4\n#error bits\n#endif\n"
+                   "typedef int (*update_fn)(qlamd_context *, const qlamd_wholebody_batch *, const double *, const qlamd_contact_update *,\n"
+                   "                         int64_t, int32_t *, int, void *);\n"
+                   "update_fn entry = qlamd_wholebody_contact_update_batch;\n"
+                   "void (*defaults)(qlamd_contact_update *) = qlamd_contact_update_default;\n"
+                   "_Static_assert(offsetof(qlamd_contact_update, release_mask) == 24, \"order\");\n"
+                   "_Static_assert(offsetof(qlamd_contact_update, touchdown_distance) == 32, \"order\");\n"
+                   "_Static_assert(offsetof(qlamd_contact_update, support_next) == 64, \"order\");\n"
+                   "_Static_assert(offsetof(qlamd_heightfield, heights) == 32, \"order\");\n")
+    subprocess.check_call(GCC + ["-c", str(src), "-o", str(tmp_path / "detection.o")])
+    # the header stands alone as well, and the version number did not move with it
+    alone = tmp_path / "alone.c"
+    alone.write_text('#include "qlamd_contact_detection.h"\nqlamd_contact_update u;\n')
+    subprocess.check_call(GCC + ["-c", str(alone), "-o", str(tmp_path / "alone.o")])
+
+
+def test_the_defaults():
+    from quadruped_locomotion_amd import contact_detection as CD, plant_contacts as PC
+    u = CD.ContactUpdate()
+    C.memset(C.byref(u), 0xAB, C.sizeof(u))
+    CD.lib().qlamd_contact_update_default(C.byref(u))
+    for member, ctype in CD.ContactUpdate._fields_:
+        want = PC.CONTACT_PULLS if member == "release_mask" else (None if ctype is C.c_void_p else 0.0)
+        assert getattr(u, member) == want, member
+    CD.lib().qlamd_contact_update_default(None)                         # a NULL struct is left alone
+
+
+def test_the_cpp_wrapper_compiles_against_the_header(tmp_path):
+    """host/qlamd/contact_detection.hpp needs qlamd.h only: a caller of the three-call loop compiles with every warning an error."""
+    src = tmp_path / "detect.cpp"
+    src.write_text('#include "qlamd/contact_detection.hpp"\n'
+                   "int run(qlamd_context *ctx) {\n"
+                   "  qlamd::host::PlantState s(3);\n  std::vector<double> tau(36), plane(12), normals(36);\n  std::vector<int32_t> st(3);\n"
+                   "  std::vector<uint8_t> report(12), sensor(12);\n"
+                   "  qlamd::host::ContactDetector d;\n"
+                   "  if (d.update.release_mask != QLAMD_CONTACT_PULLS || d.update.gap != nullptr) return -1;\n"
+                   "  d.update.plane = plane.data();\n  d.update.liftoff_distance = 0.01;\n  d.update.contact_sensor = sensor.data();\n"
+                   "  d.update.surface_normal = normals.data();\n"
+                   "  int rc = qlamd::host::step_with_contacts(ctx, s, tau.data(), 9.81, 0.0025, 400.0, st.data(), nullptr, report.data(), 0.6);\n"
+                   "  if (rc != QLAMD_OK) return rc;\n"
+                   "  return qlamd::host::detect_contacts(ctx, s, d, report.data(), st.data());\n}\n")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "quadruped_locomotion_amd", "host"), "-c", str(src), "-o", str(tmp_path / "detect.o")])
+
+
+# ---- what the wrappers hand to the entry ----------------------------------------------------------------------------------------
+
+class Recorder:
+    """Stands in for the loaded library (tests/test_plant_contacts_cpu.py's): the entry records its arguments as it would see them
+    while the call is in progress -- scalars by value, structs read back member by member from the recorded byref -- and returns 0."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("qlamd_"):
+            raise AttributeError(name)
+
+        def fn(*args):
+            self.calls.append((name, [self.snap(v) for v in args]))
+            return 0
+        fn.__name__ = name
+        return fn
+
+    @staticmethod
+    def snap(v):
+        if hasattr(v, "_obj"):
+            v = v._obj
+        if isinstance(v, C.Structure):
+            return {n: getattr(v, n) for n, _ in v._fields_}
+        return v.value if isinstance(v, C._SimpleCData) else v
+
+
+def p(a):
+    if a is None:
+        return None
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+def f64(*shape):
+    return np.arange(int(np.prod(shape)), dtype=np.float64).reshape(shape) + 1.0
+
+
+WB = dict(q="joint_position", qd="joint_velocity", base_quat="base_orientation", base_linvel="base_linear_velocity",
+          base_angvel="base_angular_velocity", stance="support_leg")
+
+
+def test_the_wrappers_marshal_the_update(monkeypatch):
+    import torch
+    from quadruped_locomotion_amd import capi, contact_detection as CD
+    rec = Recorder()
+    monkeypatch.setattr(capi, "_lib", rec)
+    ctx = capi.Context()
+    ctx._h = C.c_void_p(0xC0FFEE)
+    B = 5
+    entry = "qlamd_wholebody_contact_update_batch"
+    s = dict(q=f64(B, 12), qd=f64(B, 12), base_quat=f64(B, 4), base_linvel=f64(B, 3), base_angvel=f64(B, 3), base_pos=f64(B, 3),
+             stance=np.ones((B, 4), np.uint8), normals=f64(B, 12), a_des=f64(B, 6))
+    plane, report = f64(B, 4), np.ones((B, 4), np.uint8)
+
+    def last():
+        name, args = rec.calls[-1]
+        assert name == entry and len(args) == 8
+        return args
+
+    def wb_is(got, state):
+        for key, member in WB.items():
+            assert got[member] == (p(state[key]) if state.get(key) is not None else None), member
+        for member in ("desired_base_acceleration", "desired_joint_acceleration", "surface_normal"):
+            assert got[member] is None, member                          # the entry ignores them; the wrapper does not pass them
+
+    # host, a plane, every output
+    out = CD.wholebody_contact_update(ctx, s, plane=plane, report=report, release_mask=3, touchdown_distance=0.01, approach_speed=0.2,
+                                      liftoff_distance=0.03, sensor_distance=0.02)
+    a = last()
+    assert a[0] == 0xC0FFEE and a[2] == p(s["base_pos"]) and a[4] == B and a[5] == p(out["status"]) and a[6] == capi.MEM_HOST and a[7] is None
+    wb_is(a[1], s)
+    assert a[3] == dict(plane=p(plane), heightfield=None, contact_report=p(report), release_mask=3, touchdown_distance=0.01,
+                        approach_speed=0.2, liftoff_distance=0.03, sensor_distance=0.02, support_next=p(out["support_next"]),
+                        contact_sensor=p(out["sensor"]), events=p(out["events"]), gap=p(out["gap"]), surface_normal=p(out["normals"]),
+                        foot_position=p(out["foot_pos"]), foot_velocity=p(out["foot_vel"]))
+    assert out["support_next"].shape == (B, 4) and out["support_next"].dtype == np.uint8 and out["normals"].shape == (B, 12)
+    assert out["support_next"] is not s["stance"]
+    # host, nothing optional: the library's defaults, no flags, only what `want` names; in place
+    bare = {k: v for k, v in s.items() if k != "stance"}
+    out = CD.wholebody_contact_update(ctx, bare, want=("gap",))
+    a = last()
+    wb_is(a[1], bare)
+    assert a[3] == dict(plane=None, heightfield=None, contact_report=None, release_mask=1, touchdown_distance=0.0, approach_speed=0.0,
+                        liftoff_distance=0.0, sensor_distance=0.0, support_next=None, contact_sensor=None, events=None, gap=p(out["gap"]),
+                        surface_normal=None, foot_position=None, foot_velocity=None)
+    out = CD.wholebody_contact_update(ctx, s, want=(), in_place=True)
+    a = last()
+    assert out["support_next"] is s["stance"] and a[3]["support_next"] == p(s["stance"]) == a[1]["support_leg"]
+    # a height field: the struct's address travels, and the struct holds the array
+    heights = f64(7, 9)
+    hf = CD.heightfield((-1.0, 2.0), 0.05, heights)
+    assert (hf.origin_x, hf.origin_y, hf.resolution, hf.nx, hf.ny, hf.heights) == (-1.0, 2.0, 0.05, 9, 7, p(heights))
+    CD.wholebody_contact_update(ctx, s, hf=hf, want=())
+    assert last()[3]["heightfield"] == C.addressof(hf) and last()[3]["plane"] is None
+    n = len(rec.calls)
+    for bad in (dict(plane=f64(B + 1, 4)), dict(report=np.ones((B, 3), np.uint8))):
+        with pytest.raises(ValueError, match=list(bad)[0]):
+            CD.wholebody_contact_update(ctx, s, **bad)
+    with pytest.raises(ValueError):
+        CD.wholebody_contact_update(ctx, dict(s, base_pos=f64(B, 4)))
+    with pytest.raises(ValueError):
+        CD.wholebody_contact_update(ctx, bare, in_place=True)
+    with pytest.raises(TypeError, match="lift_distance"):
+        CD.wholebody_contact_update(ctx, s, lift_distance=0.1)
+    with pytest.raises(ValueError):
+        CD.heightfield((0.0, 0.0), 0.05, np.zeros((4, 4), np.float32))
+    assert len(rec.calls) == n
+
+    # device
+    d = {k: torch.from_numpy(v) for k, v in s.items()}
+    st = torch.zeros(B, dtype=torch.int32)
+    dplane, dreport = torch.from_numpy(plane), torch.from_numpy(report)
+    o = dict(support_next=torch.zeros(B, 4, dtype=torch.uint8), sensor=torch.zeros(B, 4, dtype=torch.uint8),
+             events=torch.zeros(B, 4, dtype=torch.uint8), gap=torch.zeros(B, 4, dtype=torch.float64),
+             normals=torch.zeros(B, 12, dtype=torch.float64), foot_pos=torch.zeros(B, 4, 3, dtype=torch.float64),
+             foot_vel=torch.zeros(B, 12, dtype=torch.float64))
+    CD.wholebody_contact_update_device(ctx, d, st, plane=dplane, report=dreport, stream=0x5151, liftoff_distance=0.5, release_mask=0, **o)
+    a = last()
+    wb_is(a[1], d)
+    assert a[2] == p(d["base_pos"]) and a[4] == B and a[5] == p(st) and a[6] == capi.MEM_DEVICE and a[7] == 0x5151
+    assert a[3] == dict(plane=p(dplane), heightfield=None, contact_report=p(dreport), release_mask=0, touchdown_distance=0.0,
+                        approach_speed=0.0, liftoff_distance=0.5, sensor_distance=0.0, support_next=p(o["support_next"]),
+                        contact_sensor=p(o["sensor"]), events=p(o["events"]), gap=p(o["gap"]), surface_normal=p(o["normals"]),
+                        foot_position=p(o["foot_pos"]), foot_velocity=p(o["foot_vel"]))
+    CD.wholebody_contact_update_device(ctx, d, st, support_next=d["stance"])
+    a = last()
+    assert a[3]["support_next"] == a[1]["support_leg"] == p(d["stance"]) and a[3]["gap"] is None and a[7] is None
+    n = len(rec.calls)
+    for bad in (dict(plane=torch.zeros(B, 3, dtype=torch.float64)), dict(gap=torch.zeros(B, 4, dtype=torch.float32)),
+                dict(normals=torch.zeros(B, 24, dtype=torch.float64)[:, ::2]), dict(sensor=torch.zeros(B + 1, 4, dtype=torch.uint8))):
+        with pytest.raises(ValueError, match=list(bad)[0]):
+            CD.wholebody_contact_update_device(ctx, d, st, **bad)
+    with pytest.raises(ValueError, match="status"):
+        CD.wholebody_contact_update_device(ctx, d, torch.zeros(B, dtype=torch.int64))
+    assert len(rec.calls) == n
+    ctx._h = C.c_void_p()
+
+
+def test_resources_are_what_design_states(tmp_path):
+    """DESIGN.md 4.6e names the new kernel's registers, private segment and LDS; the figures are the code-object metadata of the
+    unit compiled with the build's flags.  At most 128 registers: four wavefronts per SIMD."""
+    from tools import kernel_isa
+    text = open(os.path.join(ROOT, "DESIGN.md")).read()
+    m = re.search(r"`contact_update_kernel`: (\d+) VGPR, (\d+) AGPR, (\d+) B private segment, (\d+) B LDS", text)
+    assert m, "DESIGN.md 4.6e does not state the kernel's resources"
+    stated = [int(x) for x in m.groups()]
+    path = kernel_isa.assemble("contact_update_kernel.hip", out=str(tmp_path / "contact_update_kernel.s"))
+    md = kernel_isa.meta(path)
+    names = [k for k in md if "contact_update_kernel" in k]
+    assert len(names) == 1
+    name = names[0]
+    lds = [int(x) for x in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", open(path).read())]
+    assert len(lds) == 1
+    got = [md[name]["vgpr"], md[name].get("agpr", 0), md[name].get("scratch", 0), lds[0]]
+    assert got == stated, (got, stated)
+    assert md[name].get("scratch", 0) == 0 and md[name]["vgpr"] + md[name].get("agpr", 0) <= 128
+    assert lds[0] == 4 * 88 * 8                                         # the model table and nothing else
+    assert not any("scratch_" in l.split(";")[0] for l in kernel_isa.kernels(path)[name])

@@ -17,8 +17,16 @@
    (the old entry's kernel), with contacts and no touchdown, and with every robot projecting; part 2 gives every tick the flags
    of the tick before as previous_support_leg (zeros at the first tick) and --velocity-gain as k_v (1/s; default 0).
 
+4. --detect [--terrain plane|heightfield] (implies --contacts): part 1 times qlamd_wholebody_contact_update_batch alone, every
+   output given, with its bytes per robot and GB/s next to those of qlamd_wholebody_dynamics_batch; part 2 runs THREE launches per
+   tick -- whole-body step, plant step with its report, contact update in place -- and the support flags and surface normals come
+   from the update, not from the trot's phase (which gives the first tick's flags only).  Every robot is lifted so that the feet
+   the trot flags at the start stand at z = 0 on average; the terrain is that plane, or a 65 x 65 height field of +-5 mm around it.
+   A foot is flagged at gap <= 0 while it does not move away, and released 10 mm above the ground or when the report says it pulls.
+   Also reported: the share of (tick, leg) pairs on which detection and the trot schedule disagree.
+
 usage: closed_loop_probe.py [--batch 4096] [--ticks 64] [--batches 4096,65536,1048576] [--steps 64] [--repeats 5] [--out file]
-                            [--contacts] [--velocity-gain K]"""
+                            [--contacts] [--velocity-gain K] [--detect] [--terrain plane|heightfield]"""
 import argparse
 import os
 import sys
@@ -40,9 +48,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--contacts", action="store_true")
     ap.add_argument("--velocity-gain", type=float, default=0.0)
+    ap.add_argument("--detect", action="store_true")
+    ap.add_argument("--terrain", choices=("plane", "heightfield"), default="plane")
     a = ap.parse_args()
+    a.contacts = a.contacts or a.detect
     import torch
     from quadruped_locomotion_amd import capi, plant_contacts, synth
+    if a.detect:
+        from quadruped_locomotion_amd import contact_detection
     ctx = capi.Context(device=0)
     stream = torch.cuda.current_stream().cuda_stream
     dev = dict(device="cuda:0")
@@ -69,6 +82,25 @@ def main():
         v = [region(fn, n) for _ in range(a.repeats + 1)][1:]
         return float(np.median(v)), max(v) - min(v)
 
+    def terrain(B):
+        """-> the terrain arguments of the contact update on the device (and what keeps them alive)"""
+        if a.terrain == "plane":
+            plane = f64(B, 4)
+            plane[:, 2] = 1.0
+            return dict(plane=plane)
+        n, res = 65, 0.05
+        x = (np.arange(n) - n // 2) * res
+        X, Y = np.meshgrid(x, x)
+        heights = torch.from_numpy(np.ascontiguousarray(0.005 * np.sin(2.0 * np.pi * X / 0.8) * np.cos(2.0 * np.pi * Y / 1.1))).to("cuda:0")
+        return dict(hf=contact_detection.heightfield((x[0], x[0]), res, heights))
+
+    def update_outputs(B):
+        u8 = lambda: torch.zeros(B, 4, dtype=torch.uint8, **dev)  # noqa: E731
+        return dict(support_next=u8(), sensor=u8(), events=u8(), gap=f64(B, 4), normals=f64(B, 12), foot_pos=f64(B, 12), foot_vel=f64(B, 12))
+
+    RULE = dict(liftoff_distance=0.01, sensor_distance=0.005)
+    UPDATE_BYTES = (96 + 96 + 32 + 24 + 24 + 24 + 4 + 4, 4 + 4 + 4 + 4 + 32 + 96 + 96 + 96)   # read (without the terrain), written
+
     say("plant step: %d launches a region, median (spread) of %d regions, us per launch" % (a.steps, a.repeats))
     for B in [int(x) for x in a.batches.split(",")]:
         n = a.steps if B <= 65536 else max(4, a.steps // 8)
@@ -93,6 +125,18 @@ def main():
         M, h, Jc = f64(B, 18, 18), f64(B, 18), f64(B, 12, 18)
         t_dyn = sample(lambda: capi.wholebody_dynamics_device(ctx, d, M, h, Jc, stream=stream), n)
         del M, h, Jc
+        if a.detect:
+            dd = dict(d, stance=torch.from_numpy(np.ascontiguousarray(s["stance"], dtype=np.uint8)).to("cuda:0"))
+            ter, o, report = terrain(B), update_outputs(B), torch.zeros(B, 4, dtype=torch.uint8, **dev)
+            call = contact_detection.ContactUpdateCall(ctx, dd, st, report=report, stream=stream, **ter, **o, **RULE)   # checked once
+            t_upd = sample(call, n)
+            del call
+            per = sum(UPDATE_BYTES) + (32 if a.terrain == "plane" else 128)   # the plane, or four cells per foot
+            say("%8d robots: qlamd_wholebody_contact_update_batch (%s, every output) %8.2f (%.2f) = %.0f GB/s of its %d B per robot (%d read, "
+                "%d written)   status OK %d / %d   | qlamd_wholebody_dynamics_batch %.0f GB/s of its 4464 B written + 304 B read per robot"
+                % (B, a.terrain, t_upd[0], t_upd[1], B * per / t_upd[0] * 1e-3, per, per - UPDATE_BYTES[1], UPDATE_BYTES[1],
+                   int((st == 0).sum()), B, B * 4768 / t_dyn[0] * 1e-3))
+            del dd, ter, o
         bytes_step = B * (272 + 96 + 4 + 24 + 144 + 96 + 296 + 4)
         say("%8d robots: nu' and f %8.2f (%.2f)   nu', f and next state %8.2f (%.2f) = %.0f GB/s of its %d B per robot   status OK %d / %d"
             "   | qlamd_wholebody_dynamics_batch (M, h, Jc) %8.2f (%.2f)"
@@ -118,14 +162,40 @@ def main():
 
     zero_flags = torch.zeros(B, 4, dtype=torch.uint8, **dev)
 
+    if a.detect:
+        # lift every robot so that the feet the trot flags at the start stand at z = 0 on average
+        d0 = capi.to_device(s)
+        o0, st0 = update_outputs(B), torch.zeros(B, dtype=torch.int32, **dev)
+        contact_detection.wholebody_contact_update_device(ctx, d0, st0, stream=stream, **o0)
+        on = stance[0].double()
+        lift = (o0["foot_pos"].reshape(B, 4, 3)[:, :, 2] * on).sum(dim=1) / on.sum(dim=1).clamp(min=1.0)
+        s = dict(s, base_pos=(d0["base_pos"] - torch.stack([torch.zeros_like(lift), torch.zeros_like(lift), lift], dim=1)).cpu().numpy())
+        ter = terrain(B)
+        disagree = []
+
     def loop(timed):
         d = capi.to_device(s)
+        if a.detect:
+            d["stance"] = stance[0].clone()
+            d["normals"] = f64(B, 12)
+            d["normals"].reshape(B, 4, 3)[:, :, 2] = 1.0
+            prev, report, st_up, o = zero_flags.clone(), zero_flags.clone(), torch.zeros(B, dtype=torch.int32, **dev), update_outputs(B)
+            update = contact_detection.ContactUpdateCall(ctx, d, st_up, report=report, stream=stream, support_next=d["stance"],
+                                                         sensor=o["sensor"], events=o["events"], gap=o["gap"], normals=d["normals"],
+                                                         **ter, **RULE)   # checked once; the tick launches it
         tau, st_qp, st_pl = f64(B, 12), torch.zeros(B, dtype=torch.int32, **dev), torch.zeros(B, dtype=torch.int32, **dev)
         mem, ws = torch.zeros(B, 4, dtype=torch.int64, **dev), torch.zeros(B, dtype=torch.int64, **dev)
         prev_ws = torch.zeros_like(ws)
         stats = []
 
         def tick(k):
+            if a.detect:
+                capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
+                plant_contacts.wholebody_plant_step_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream, velocity_gain=a.velocity_gain,
+                                                           prev_stance=prev, friction=0.6, report=report)
+                prev.copy_(d["stance"])
+                update()
+                return
             d["stance"] = stance[k]
             capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
             if a.contacts:
@@ -144,11 +214,15 @@ def main():
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) * 1e3 / K
         for k in range(K):
+            ran_with = d["stance"].clone() if a.detect else stance[k]
             tick(k)
             torch.cuda.synchronize()
             same = float((ws == prev_ws).float().mean()) if k else float("nan")
             prev_ws.copy_(ws)
-            speed = held_foot_speeds(d, stance[k])
+            if a.detect:
+                disagree.append((float((ran_with != stance[k]).float().mean()), int((o["events"] & 1).ne(0).sum()),
+                                 int((o["events"] & 2).ne(0).sum()), int((o["events"] & 4).ne(0).sum()), int((st_up == 0).sum())))
+            speed = held_foot_speeds(d, ran_with)
             speed = speed[torch.isfinite(speed)]
             stats.append((int((st_qp == 0).sum()), int((st_pl == 0).sum()), same, bool(torch.isfinite(d["q"]).all()),
                           float(speed.max()), float(speed.median())))
@@ -159,7 +233,15 @@ def main():
     say("closed loop: %d trot robots, %d ticks of qlamd_wholebody_solve_placed_batch (table) -> plant step in place (%s), dt %.4f s; "
         "support set switched per tick %.4f"
         % (B, K, "with contacts, k_v = %g / s" % a.velocity_gain if a.contacts else "qlamd_wholebody_forward_dynamics_batch", DT, switched))
-    say("  us per tick (two launches): %s median %.2f spread %.2f" % (" ".join("%.2f" % x for x in t), float(np.median(t)), max(t) - min(t)))
+    if a.detect:
+        say("  three launches per tick: the flags and normals come from qlamd_wholebody_contact_update_batch (%s; released at 10 mm or by a "
+            "pulling report), the trot's phase gives the first tick's flags only" % a.terrain)
+        say("  detection against the trot schedule: share of (tick, leg) pairs that disagree %.4f (first quarter %.4f, last quarter %.4f); "
+            "per tick and robot: touchdowns %.4f, released by the report %.4f, by the gap %.4f; contact update OK %.4f"
+            % (np.mean([x[0] for x in disagree]), np.mean([x[0] for x in disagree[:max(1, K // 4)]]), np.mean([x[0] for x in disagree[-max(1, K // 4):]]),
+               np.mean([x[1] for x in disagree]) / B, np.mean([x[2] for x in disagree]) / B, np.mean([x[3] for x in disagree]) / B,
+               np.mean([x[4] for x in disagree]) / B))
+    say("  us per tick (%s launches): %s median %.2f spread %.2f" % ("three" if a.detect else "two", " ".join("%.2f" % x for x in t), float(np.median(t)), max(t) - min(t)))
     q = max(1, K // 4)
     for lo in range(0, K, q):
         part = stats[lo:lo + q]
