@@ -510,8 +510,11 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
       //      a row left out, or a leg without a row, has 1 / d_k := 0, and with it its column of L, its step and its update are
       //      exact zeros.  The steps t_k come from the slacks, eliminated with the same L;
       //   3. the directions corrected in place, z~_k = z_k - sum_{j<k} L[k][j] z~_j, and r~_k the same way with -1 on the lane of
-      //      the slot a row has just taken (its entry of N* is + z~'/d): plain FMAs, L is on every lane.  x, u and the slots are
-      //      stepped row by row as before -- the same values in the same slot order;
+      //      the slot a row has just taken (its entry of N* is + z~'/d): plain FMAs, L is on every lane.  x and u are stepped row
+      //      by row as before.  The slots: lowest free lane first where a robot of the wavefront builds its set (kWithGreedy),
+      //      by a fixed map -- leg k's row of round r on lane kLegs * r + k -- everywhere else, with the slot words (used, q, ids,
+      //      active mask) rebuilt behind the last round instead of kept in it (kFixed below; a round 378 -> 316 instructions,
+      //      profiles/r14/install_rounds_slots.txt; tests/test_install_rounds_slots_cpu.py is the bookkeeping in numpy);
       //   4. the four rank-one updates of H and N* as one stream of 4 x 24 broadcast-FMAs with nothing between them.
       // Row after row (the form this replaces, kept for kTorque below) the round was one chain: the pivot of row k + 1 waited for
       // the correction by row k, that for row k's reciprocal, that for row k's quad sum, four times, with the 96 update FMAs between
@@ -530,10 +533,53 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
       // code they were: folded into one loop the selection costs the static bench batch 0.25 us a step)
       const auto rounds = [&](auto WithGreedy) {
       constexpr bool kWithGreedy = decltype(WithGreedy)::value;
+      // kFixed: the block form without a robot that builds its set.  The set is on every lane before the first round, so what
+      // the rounds will hold is decoded HERE, once: where component c of my leg's row of each round lies in the normals table
+      // (the zero of the robot's block for a leg without a row and for the spare lane of a quad: no select on the way), whether
+      // my leg's first row is the minimum-force row (kind 0 is the lowest bit, so only round 0 can bring it: the one offset
+      // that is not 0), how many rounds the wavefront takes, and the row that would take MY slot lane.  Slots follow a fixed map:
+      // the row of leg k in round r goes to slot lane kLegs * r + k (< kV, as the refinement's export needs; a row left out
+      // leaves its lane free -- slots are not compact after a drop either, their order only breaks exact ties).  A round then
+      // keeps what its arithmetic needs (ok, 1 / d_k, the steps, the -1 and the step on the new slot's lane) and ONE flag per
+      // lane, "my slot lane was taken"; used, q, the ids and the active mask are rebuilt from the flags behind the loop.
+      // The table is read a round ahead (one ds_read_b64 whose latency the round in front covers).  latch() zeroes entries of
+      // the table, but only for rows that have FINISHED, and no row finishes before the first selection behind the warm block.
+      constexpr bool kFixed = !kWithGreedy && !kTorque;
+      const double *nrm_next = lds_row + kZeroSlot, *nrm_last = lds_row + kZeroSlot;
+      double nv_ahead = 0.0;
+      bool min_first = false, slot_taken = false;
+      int nrounds = 0, slot_id = 0;
+      if constexpr (kFixed) {
+        const double *const zero_at = lds_row + kZeroSlot;
+        const double *const tab_at = lds_nrm + ((int)threadIdx.x & 63);
+        unsigned rest = mine;
+        const double *at[3];
+        static_for<3>([&](auto R) {
+          at[R] = (rest != 0u && comp) ? tab_at + 64 * (__ffs((int)rest) - 1) : zero_at;
+          rest &= rest - 1u;
+        });
+        nv_ahead = *at[0];
+        nrm_next = at[1];
+        nrm_last = at[2];
+        min_first = (mine & 1u) != 0u;
+        const int n_mine = __popc(mine);
+        nrounds = __builtin_amdgcn_ballot_w64(n_mine > 2) != 0ull ? 3 : __builtin_amdgcn_ballot_w64(n_mine > 1) != 0ull ? 2
+                  : __builtin_amdgcn_ballot_w64(n_mine > 0) != 0ull ? 1 : 0; // (scalar)
+        // the row of slot lane lr = kLegs * r + k: the (r + 1)-th row of leg k
+        const int sr = lr / kLegs, sk = lr % kLegs;
+        unsigned srows = (unsigned)((wm >> (kKinds * sk)) & kLegRows);
+        srows &= sr >= 1 ? srows - 1u : ~0u;
+        srows &= sr >= 2 ? srows - 1u : ~0u;
+        slot_id = kKinds * sk + __ffs((int)srows) - 1; // (without such a row: never taken, never read)
+      }
       for (int round = 0;; round++) {
-        bool have = mine != 0u;
-        int kind = have ? __ffs((int)mine) - 1 : 0;
-        mine &= mine - 1u;
+        bool have = false;
+        int kind = 0;
+        if constexpr (!kFixed) {
+          have = mine != 0u;
+          kind = have ? __ffs((int)mine) - 1 : 0;
+          mine &= mine - 1u;
+        }
         if constexpr (kWithGreedy) {
           // a robot that builds its set: the most violated row of my leg that is not in the set yet, by the keys of the
           // selection (update_and_select) reduced over the quad instead of the row
@@ -563,11 +609,21 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
             kind = greedy ? gkind : kind;
           }
         }
-        if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
+        if constexpr (kFixed) {
+          if (round == nrounds) break;
+        } else {
+          if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
+        }
         // component c of my leg's row and its offset: n'x - b >= 0 with b = f_min (kind 0), 0 (friction), and for the torque bounds
         // of joint k (kinds 5 + 2k upper, 6 + 2k lower) n = +-J[:,k], b = -(tau_max -+ tau0_k) -- held by the joint's lane
-        double nv, bp;
-        {
+        double nv = 0.0, bp = 0.0;
+        unsigned kinds = 0u;
+        if constexpr (kFixed) {
+          npj = nv_ahead;
+          nv_ahead = *nrm_next;
+          nrm_next = nrm_last;
+          bp = sel(round == 0 && min_first, f_min, 0.0);
+        } else {
           const double fr = sel(kind == 1, myt1, sel(kind == 2, -myt1, sel(kind == 3, myt2, -myt2)));
           nv = sel(kind == 0, myn, fma(mu, myn, fr));
           bp = sel(kind == 0, f_min, 0.0);
@@ -580,15 +636,17 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
             const double bl = sel(kj == 0, quad_bc<0>(Q.tq_lo), sel(kj == 1, quad_bc<1>(Q.tq_lo), quad_bc<2>(Q.tq_lo)));
             bp = sel(tq, -sel(lower, bl, bu), bp);
           }
+          npj = sel(have && comp, nv, 0.0);
+          bp = sel(have, bp, 0.0);
+          // which row every leg brings, for all lanes of the robot: (kind + 1) in four bits per leg, OR-ed over the row
+          kinds = (have && c == 0) ? (unsigned)(kind + 1) << (4 * leg) : 0u;
+          static_for<4>([&](auto K) {
+            constexpr int ctrl = K == 0 ? 0x128 : K == 1 ? 0x124 : K == 2 ? 0x122 : 0x121;
+            kinds |= (unsigned)__builtin_amdgcn_mov_dpp((int)kinds, ctrl, 0xF, 0xF, true);
+          });
         }
-        npj = sel(have && comp, nv, 0.0);
-        // which row every leg brings, for all lanes of the robot: (kind + 1) in four bits per leg, OR-ed over the row
-        unsigned kinds = (have && c == 0) ? (unsigned)(kind + 1) << (4 * leg) : 0u;
-        static_for<4>([&](auto K) {
-          constexpr int ctrl = K == 0 ? 0x128 : K == 1 ? 0x124 : K == 2 ? 0x122 : 0x121;
-          kinds |= (unsigned)__builtin_amdgcn_mov_dpp((int)kinds, ctrl, 0xF, 0xF, true);
-        });
-        double sl = quad_sum(npj * x) - sel(have, bp, 0.0); // slack of my leg's row at x, kept up to date through the round
+        const int slot0 = lr - kLegs * round; // kFixed: leg k's row of this round takes the slot lane with slot0 == k
+        double sl = quad_sum(npj * x) - bp; // slack of my leg's row at x, kept up to date through the round
         double za[kLegs], ra[kLegs];
 #pragma unroll
         for (int m = 0; m < kLegs; m++) { za[m] = 0.0; ra[m] = 0.0; }
@@ -612,7 +670,7 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
           double W[kLegs][kLegs], L[kLegs][kLegs], zi[kLegs], tw[kLegs];
           static_for<kLegs>([&](auto K) {
             constexpr int k = K;
-            const int kk = (int)((kinds >> (4 * k)) & 15u) - 1; // leg k's row of this round (-1: none)
+            const int kk = (int)((kinds >> (4 * k)) & 15u) - 1; // leg k's row of this round (-1: none; kFixed: not decoded)
             double dk = D[k][k], s = sk[k];
             static_for<k>([&](auto J) {
               constexpr int j = J;
@@ -621,8 +679,9 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
             });
             // a row that depends on the rows installed before it (this round's earlier ones included) is left out: z'n_p is then
             // rounding noise, which with the entries of H reaching 1 / w_reg = 1e4 means up to 1e-10, while an independent row has
-            // z'n_p >= |n|^2 / trace(G) ~ 1e-3
-            const bool ok = kk >= 0 && dk > 1e-6;
+            // z'n_p >= |n|^2 / trace(G) ~ 1e-3.  (kFixed asks d_k alone: a leg without a row has n_k = 0 on its lanes, so z_k and
+            // row and column k of D are exact zeros, and with them W[k][.] and d_k)
+            const bool ok = (kFixed || kk >= 0) && dk > 1e-6;
             const double okf = sel(ok, 1.0, 0.0);
             zi[k] = rcp_nr1(sel(ok, dk, 1.0)) * okf;            // 1 / d_k, or 0
             tw[k] = -s * zi[k];
@@ -642,17 +701,26 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
             za[k] *= okf;
             const double rr = ra[k] * okf;
             x = fma(tw[k], za[k], x);
-            u = fma(-tw[k], rr, u);
-            const int newlane = __ffs(~used & 0xFFFu) - 1;
-            const bool newslot = ok && lr == newlane;
-            const int pk = kKinds * k + kk;
-            ra[k] = sel(newslot, -1.0, rr);
-            u = sel(newslot, tw[k], u);
-            idk = newslot ? pk : idk;
-            used |= ok ? (1u << newlane) : 0u;
-            act_mask |= ok ? (one << pk) : 0;
+            if constexpr (kFixed) {
+              // (the multiplier of the new slot needs no select: a free lane's row of N* is 0, so its r~ and its u are exact
+              // zeros until the lane is taken -- once, by the fixed map -- and the -1 it then holds makes u = 0 + t_k there)
+              const bool newslot = ok & (slot0 == k); // (& and |: plain mask arithmetic, nothing to branch on)
+              ra[k] = sel(newslot, -1.0, rr);
+              u = fma(-tw[k], ra[k], u);
+              slot_taken = slot_taken | newslot;
+            } else {
+              u = fma(-tw[k], rr, u);
+              const int newlane = __ffs(~used & 0xFFFu) - 1;
+              const bool newslot = ok && lr == newlane;
+              const int pk = kKinds * k + kk;
+              ra[k] = sel(newslot, -1.0, rr);
+              u = sel(newslot, tw[k], u);
+              idk = newslot ? pk : idk;
+              used |= ok ? (1u << newlane) : 0u;
+              act_mask |= ok ? (one << pk) : 0;
+              q += ok ? 1 : 0;
+            }
             rnorm2 = vmax(rnorm2, dk); // (a row left out has d_k <= 1e-6 < R_norm^2)
-            q += ok ? 1 : 0;
           });
           // the four rank-one updates, H -= z~_k z~_k' / d_k and N* -= r~_k z~_k' / d_k, as one stream: nothing between them
           static_for<kLegs>([&](auto K) {
@@ -710,6 +778,19 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
           }
           update_only();
         });
+      }
+      if constexpr (kFixed) {
+        // the bookkeeping of all rounds in one step: the slot lanes that were taken are the robot's 16 bits of one ballot
+        const unsigned long long taken_m = __builtin_amdgcn_ballot_w64(slot_taken);
+        used = (unsigned)(taken_m >> ((int)threadIdx.x & 48)) & 0xFFFFu;
+        q = __popc(used);
+        idk = slot_taken ? slot_id : 0;
+        unsigned rows_in = slot_taken ? 1u << slot_id : 0u; // OR-ed over the row: the rows that went in
+        static_for<4>([&](auto K) {
+          constexpr int ctrl = K == 0 ? 0x128 : K == 1 ? 0x124 : K == 2 ? 0x122 : 0x121;
+          rows_in |= (unsigned)__builtin_amdgcn_mov_dpp((int)rows_in, ctrl, 0xF, 0xF, true);
+        });
+        act_mask = (mask_t)rows_in;
       }
       };
       if constexpr (kGreedy) {
