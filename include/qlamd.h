@@ -979,5 +979,7 @@ int qlamd_version(void);
 #include "qlamd_plant_contacts.h"
 /* ground contact detection for the plant (QLAMD_HAS_CONTACT_DETECTION, qlamd_wholebody_contact_update_batch): likewise */
 #include "qlamd_contact_detection.h"
+/* the plant step with friction (QLAMD_HAS_PLANT_FRICTION, qlamd_wholebody_plant_step_friction_batch): likewise */
+#include "qlamd_plant_friction.h"
 
 #endif /* QLAMD_H */

@@ -56,7 +56,8 @@ typedef struct qlamd_heightfield {
  * finite, or heights NULL; a distance or the speed not finite; liftoff_distance < touchdown_distance; batch < 0.
  * Memory spaces, streams, QLAMD_ERR_BUSY and capture as for qlamd_wholebody_plant_step_batch: a QLAMD_MEM_DEVICE call uses no
  * scratch of the context's and can be captured into a graph.
- * Not built: position-level drift correction of a held foot, and friction as a constraint. */
+ * Friction as a constraint is qlamd_wholebody_plant_step_friction_batch (qlamd_plant_friction.h), whose report releases a foot with
+ * release_mask = QLAMD_CONTACT_SEPARATING.  Not built: position-level drift correction of a held foot. */
 typedef struct qlamd_contact_update {
   /* in */
   const double *plane;                  /* [B][4] (a, b, c, d): ground a x + b y + c z = d per robot, or NULL */

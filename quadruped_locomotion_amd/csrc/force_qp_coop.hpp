@@ -133,9 +133,12 @@ __device__ __forceinline__ void force_qp_objective(const double S[6], double w_r
 // method runs as always, so a set that no longer fits costs passes, not the answer (the minimiser is unique).  The passes a
 // robot then still needs are its `iters_out`.  QuadProg++ has no such entry (solve_quadprog always starts from the
 // unconstrained minimiser, QuadProg++.cc:216-233): iteration counts no longer match the reference's one for one, torques do.
-template <bool kTorque, bool kWarm = false, int kLegs = 4, bool kRounds = true>
+// kGivenInverse (the plant step with friction, plant_friction_coop.hpp: two QPs on one G): Hgiven is my row of G^-1 as the caller
+// has it already and Hbad what its pivots said, so the elimination below is not emitted; c2, which only feeds the termination
+// tolerance, is then the sum of sqrt(diag G^-1) >= trace(J).  A cold start then also writes its final working set to ws_out.
+template <bool kTorque, bool kWarm = false, int kLegs = 4, bool kRounds = true, bool kGivenInverse = false>
 __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, double *lds_nrm, double &x, int &iters_out,
-                                             unsigned long long *ws_out = nullptr) {
+                                             unsigned long long *ws_out = nullptr, const double *Hgiven = nullptr, bool Hbad = false) {
   using mask_t = std::conditional_t<kTorque, unsigned long long, unsigned>;
   constexpr int kKinds = kTorque ? 11 : 5;
   // kLegs: the legs that can support, in rows 0 .. kLegs-1 of the 16-lane row (the callers put the support legs first: a
@@ -162,37 +165,45 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
       for (int j = 0; j < kV; j++) diag = (j == myidx) ? Gm[j] : diag;
       c1 = row_sum(sel(row_on, diag, 0.0));
     }
-    // in-place Gauss-Jordan inversion, row per lane; pivot k = L_kk^2 of the Cholesky factor.
-    // Row update H[j] -= f * H_k[j] is one v_fmac_f64_dpp (pivot row read through the DPP operand);
-    // on the pivot lane f = 1 - 1/d turns the same formula into H_k[j] / d.
     bool bad = false;
-    double my_pivot = 1.0; // pivot of my own row, for c2 below
-    // The chain pivot -> reciprocal -> factor -> row updates -> next pivot is serial; the column of the NEXT pivot is
-    // updated first, so that its reciprocal (hardware seed + one Newton step, 2e-15: the final refinement works on
-    // G itself, not on this inverse) is under way while the other ten columns are still being updated.
-    double d = bcv<0>(H[0]);
-    static_for<kV>([&](auto K) {
-      constexpr int k = K;
-      bad = bad || !(d > 0.0);
-      const double p = rcp_nr1(d);
-      const bool piv = comp && (myidx == k);
-      my_pivot = piv ? d : my_pivot;
-      const double f = piv ? (1.0 - p) : H[k] * p;
-      const double nf = -f;
-      if constexpr (k < kV - 1) {
-        fmac_bc<lane_of(k), true>(H[k + 1], H[k + 1], nf);
-        d = bcv<k + 1>(H[k + 1]);
-      }
-      static_for<kV>([&](auto J) {
-        constexpr int j = J;
-        if constexpr (j != k && j != k + 1) fmac_bc<lane_of(k), (k == kV - 1 && j == 0)>(H[j], H[j], nf);
+    if constexpr (kGivenInverse) {
+      double hd = 0.0;
+#pragma unroll
+      for (int j = 0; j < kV; j++) { H[j] = Hgiven[j]; hd = (j == myidx) ? Hgiven[j] : hd; }
+      c2 = row_sum(sel(row_on, sqrt(hd), 0.0));
+      bad = Hbad;
+    } else {
+      // in-place Gauss-Jordan inversion, row per lane; pivot k = L_kk^2 of the Cholesky factor.
+      // Row update H[j] -= f * H_k[j] is one v_fmac_f64_dpp (pivot row read through the DPP operand);
+      // on the pivot lane f = 1 - 1/d turns the same formula into H_k[j] / d.
+      double my_pivot = 1.0; // pivot of my own row, for c2 below
+      // The chain pivot -> reciprocal -> factor -> row updates -> next pivot is serial; the column of the NEXT pivot is
+      // updated first, so that its reciprocal (hardware seed + one Newton step, 2e-15: the final refinement works on
+      // G itself, not on this inverse) is under way while the other ten columns are still being updated.
+      double d = bcv<0>(H[0]);
+      static_for<kV>([&](auto K) {
+        constexpr int k = K;
+        bad = bad || !(d > 0.0);
+        const double p = rcp_nr1(d);
+        const bool piv = comp && (myidx == k);
+        my_pivot = piv ? d : my_pivot;
+        const double f = piv ? (1.0 - p) : H[k] * p;
+        const double nf = -f;
+        if constexpr (k < kV - 1) {
+          fmac_bc<lane_of(k), true>(H[k + 1], H[k + 1], nf);
+          d = bcv<k + 1>(H[k + 1]);
+        }
+        static_for<kV>([&](auto J) {
+          constexpr int j = J;
+          if constexpr (j != k && j != k + 1) fmac_bc<lane_of(k), (k == kV - 1 && j == 0)>(H[j], H[j], nf);
+        });
+        H[k] = piv ? p : nf;
       });
-      H[k] = piv ? p : nf;
-    });
-    // c2 = trace(J) = sum over the stance rows of 1/sqrt(pivot): one rsqrt per lane instead of one per pivot
-    // (it only feeds the termination tolerance psi_tol)
-    const double rp = rsqrt_nr(my_pivot);
-    c2 = row_sum(sel(row_on, rp, 0.0));
+      // c2 = trace(J) = sum over the stance rows of 1/sqrt(pivot): one rsqrt per lane instead of one per pivot
+      // (it only feeds the termination tolerance psi_tol)
+      const double rp = rsqrt_nr(my_pivot);
+      c2 = row_sum(sel(row_on, rp, 0.0));
+    }
     if (bad && nS > 0) { iters_out = 0; return kStatusNotPd; }
   }
 
@@ -1067,7 +1078,7 @@ __device__ __forceinline__ int force_qp_coop(const ForceQp &Q, double *lds_row, 
     if constexpr (kWarm) warm_updates = reinterpret_cast<const int *>(lds_row + kWarmSlot)[0];
     iters_out = (b.x >> 8) + warm_updates; // what this robot cost: the installs and drops of a warm start count as passes
   }
-  if constexpr (kWarm) { // the final working set as a bit mask: the OR over the slot lanes of a row
+  if constexpr (kWarm || kGivenInverse) { // the final working set as a bit mask: the OR over the slot lanes of a row
     const mask_t mine = ((used >> lr) & 1u) ? (one_v<mask_t> << idk) : 0;
     unsigned lo = (unsigned)mine, hi = 0u;
     if constexpr (kTorque) hi = (unsigned)((unsigned long long)mine >> 32);

@@ -24,9 +24,15 @@
    the trot flags at the start stand at z = 0 on average; the terrain is that plane, or a 65 x 65 height field of +-5 mm around it.
    A foot is flagged at gap <= 0 while it does not move away, and released 10 mm above the ground or when the report says it pulls.
    Also reported: the share of (tick, leg) pairs on which detection and the trot schedule disagree.
+5. --friction (implies --contacts; with or without --detect): the plant step of part 2 is qlamd_wholebody_plant_step_friction_batch
+   with mu = 0.6 -- impulses and forces inside the friction pyramid -- and with --detect the update releases a foot on
+   QLAMD_CONTACT_SEPARATING instead of QLAMD_CONTACT_PULLS.  Part 1 adds the new kernel alone, next to the contacts entry's, in two
+   settings: the drawn states with the controller's own torques (qlamd_wholebody_solve_batch: the working sets are mostly empty)
+   and with the random torques of the other rows, each without a touchdown and with every robot projecting, with the distribution
+   of `iterations`.  Part 2 also reports the separating and sliding legs per tick and robot.
 
 usage: closed_loop_probe.py [--batch 4096] [--ticks 64] [--batches 4096,65536,1048576] [--steps 64] [--repeats 5] [--out file]
-                            [--contacts] [--velocity-gain K] [--detect] [--terrain plane|heightfield]"""
+                            [--contacts] [--velocity-gain K] [--detect] [--terrain plane|heightfield] [--friction]"""
 import argparse
 import os
 import sys
@@ -50,12 +56,16 @@ def main():
     ap.add_argument("--velocity-gain", type=float, default=0.0)
     ap.add_argument("--detect", action="store_true")
     ap.add_argument("--terrain", choices=("plane", "heightfield"), default="plane")
+    ap.add_argument("--friction", action="store_true")
     a = ap.parse_args()
-    a.contacts = a.contacts or a.detect
+    a.contacts = a.contacts or a.detect or a.friction
     import torch
     from quadruped_locomotion_amd import capi, plant_contacts, synth
     if a.detect:
         from quadruped_locomotion_amd import contact_detection
+    if a.friction:
+        from quadruped_locomotion_amd import plant_friction
+    MU = 0.6
     ctx = capi.Context(device=0)
     stream = torch.cuda.current_stream().cuda_stream
     dev = dict(device="cuda:0")
@@ -99,6 +109,8 @@ def main():
         return dict(support_next=u8(), sensor=u8(), events=u8(), gap=f64(B, 4), normals=f64(B, 12), foot_pos=f64(B, 12), foot_vel=f64(B, 12))
 
     RULE = dict(liftoff_distance=0.01, sensor_distance=0.005)
+    if a.friction and a.detect:
+        RULE["release_mask"] = plant_friction.CONTACT_SEPARATING
     UPDATE_BYTES = (96 + 96 + 32 + 24 + 24 + 24 + 4 + 4, 4 + 4 + 4 + 4 + 32 + 96 + 96 + 96)   # read (without the terrain), written
 
     say("plant step: %d launches a region, median (spread) of %d regions, us per launch" % (a.steps, a.repeats))
@@ -121,6 +133,23 @@ def main():
             say("%8d robots: qlamd_wholebody_plant_step_batch, nu', f and next state: contacts NULL %8.2f (%.2f)   contacts, no touchdown "
                 "%8.2f (%.2f)   every robot projecting %8.2f (%.2f)   status OK %d / %d"
                 % (B, t_null[0], t_null[1], t_quiet[0], t_quiet[1], t_proj[0], t_proj[1], int((st == 0).sum()), B))
+        if a.friction:
+            it = torch.zeros(B, 2, dtype=torch.int32, **dev)
+            tau_c = f64(B, 12)
+            capi.wholebody_solve_device(ctx, d, tau_c, None, st, stream=stream)
+            now = torch.from_numpy(np.ascontiguousarray(s["stance"], dtype=np.uint8)).to("cuda:0")
+            for name, tq in (("the controller's torques", tau_c), ("random torques", tau)):
+                res = []
+                for prev in (now, zeros):
+                    res.append(sample(lambda: plant_friction.wholebody_plant_step_friction_device(
+                        ctx, d, tq, st, MU, prev_stance=prev, velocity_gain=a.velocity_gain, iterations=it, **kw), n))
+                    hist = [torch.bincount(it[:, j].clamp(0, 31).long(), minlength=32).tolist() for j in range(2)]
+                    res.append((int((st == 0).sum()), [" ".join("%d:%d" % (k, c) for k, c in enumerate(h_) if c) for h_ in hist]))
+                say("%8d robots: qlamd_wholebody_plant_step_friction_batch, mu %.1f, %s: no touchdown %8.2f (%.2f) status OK %d / %d   every "
+                    "robot projecting %8.2f (%.2f) status OK %d / %d" % (B, MU, name, res[0][0], res[0][1], res[1][0], B, res[2][0], res[2][1], res[3][0], B))
+                say("           iterations (count:robots) no touchdown: force QP %s | projecting: impulse QP %s ; force QP %s"
+                    % (res[1][1][1], res[3][1][0], res[3][1][1]))
+            del it, tau_c
         del nxt
         M, h, Jc = f64(B, 18, 18), f64(B, 18), f64(B, 12, 18)
         t_dyn = sample(lambda: capi.wholebody_dynamics_device(ctx, d, M, h, Jc, stream=stream), n)
@@ -186,19 +215,28 @@ def main():
         tau, st_qp, st_pl = f64(B, 12), torch.zeros(B, dtype=torch.int32, **dev), torch.zeros(B, dtype=torch.int32, **dev)
         mem, ws = torch.zeros(B, 4, dtype=torch.int64, **dev), torch.zeros(B, dtype=torch.int64, **dev)
         prev_ws = torch.zeros_like(ws)
+        report_f = report if a.detect else zero_flags.clone()   # (--friction without --detect: the report is only counted)
         stats = []
 
         def tick(k):
             if a.detect:
                 capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
-                plant_contacts.wholebody_plant_step_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream, velocity_gain=a.velocity_gain,
-                                                           prev_stance=prev, friction=0.6, report=report)
+                if a.friction:
+                    plant_friction.wholebody_plant_step_friction_device(ctx, d, tau, st_pl, MU, dt=DT, next=d, stream=stream,
+                                                                        velocity_gain=a.velocity_gain, prev_stance=prev, report=report)
+                else:
+                    plant_contacts.wholebody_plant_step_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream, velocity_gain=a.velocity_gain,
+                                                               prev_stance=prev, friction=MU, report=report)
                 prev.copy_(d["stance"])
                 update()
                 return
             d["stance"] = stance[k]
             capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
-            if a.contacts:
+            if a.friction:
+                plant_friction.wholebody_plant_step_friction_device(ctx, d, tau, st_pl, MU, dt=DT, next=d, stream=stream,
+                                                                    velocity_gain=a.velocity_gain, prev_stance=stance[k - 1] if k else zero_flags,
+                                                                    report=report_f)
+            elif a.contacts:
                 plant_contacts.wholebody_plant_step_device(ctx, d, tau, st_pl, dt=DT, next=d, stream=stream, velocity_gain=a.velocity_gain,
                                                  prev_stance=stance[k - 1] if k else zero_flags)
             else:
@@ -226,16 +264,25 @@ def main():
             speed = speed[torch.isfinite(speed)]
             stats.append((int((st_qp == 0).sum()), int((st_pl == 0).sum()), same, bool(torch.isfinite(d["q"]).all()),
                           float(speed.max()), float(speed.median())))
+            if a.friction:
+                cone.append((int((report_f & 8).ne(0).sum()), int((report_f & 16).ne(0).sum())))
         return stats
 
+    cone = []
     stats = loop(False)
     t = [loop(True) for _ in range(a.repeats + 1)][1:]
     say("closed loop: %d trot robots, %d ticks of qlamd_wholebody_solve_placed_batch (table) -> plant step in place (%s), dt %.4f s; "
         "support set switched per tick %.4f"
         % (B, K, "with contacts, k_v = %g / s" % a.velocity_gain if a.contacts else "qlamd_wholebody_forward_dynamics_batch", DT, switched))
+    if a.friction:
+        q4 = max(1, K // 4)
+        say("  the plant step is qlamd_wholebody_plant_step_friction_batch, mu %.1f; per tick and robot: separating legs %.4f, sliding legs %.4f "
+            "(first quarter %.4f / %.4f, last quarter %.4f / %.4f)"
+            % (MU, np.mean([c[0] for c in cone]) / B, np.mean([c[1] for c in cone]) / B, np.mean([c[0] for c in cone[:q4]]) / B,
+               np.mean([c[1] for c in cone[:q4]]) / B, np.mean([c[0] for c in cone[-q4:]]) / B, np.mean([c[1] for c in cone[-q4:]]) / B))
     if a.detect:
         say("  three launches per tick: the flags and normals come from qlamd_wholebody_contact_update_batch (%s; released at 10 mm or by a "
-            "pulling report), the trot's phase gives the first tick's flags only" % a.terrain)
+            "%s report), the trot's phase gives the first tick's flags only" % (a.terrain, "separating" if a.friction else "pulling"))
         say("  detection against the trot schedule: share of (tick, leg) pairs that disagree %.4f (first quarter %.4f, last quarter %.4f); "
             "per tick and robot: touchdowns %.4f, released by the report %.4f, by the gap %.4f; contact update OK %.4f"
             % (np.mean([x[0] for x in disagree]), np.mean([x[0] for x in disagree[:max(1, K // 4)]]), np.mean([x[0] for x in disagree[-max(1, K // 4):]]),
