@@ -57,7 +57,8 @@ typedef struct qlamd_heightfield {
  * Memory spaces, streams, QLAMD_ERR_BUSY and capture as for qlamd_wholebody_plant_step_batch: a QLAMD_MEM_DEVICE call uses no
  * scratch of the context's and can be captured into a graph.
  * Friction as a constraint is qlamd_wholebody_plant_step_friction_batch (qlamd_plant_friction.h), whose report releases a foot with
- * release_mask = QLAMD_CONTACT_SEPARATING.  Not built: position-level drift correction of a held foot. */
+ * release_mask = QLAMD_CONTACT_SEPARATING.  Position-level drift correction of a held foot is qlamd_contact_anchor.h:
+ * qlamd_wholebody_contact_update_anchored_batch keeps an anchor per leg and qlamd_wholebody_plant_step_anchored_batch holds it. */
 typedef struct qlamd_contact_update {
   /* in */
   const double *plane;                  /* [B][4] (a, b, c, d): ground a x + b y + c z = d per robot, or NULL */

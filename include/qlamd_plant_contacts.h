@@ -29,7 +29,8 @@ extern "C" {
  *      in->surface_normal given (this entry reads it; the old entry ignores it), the base's z axis with NULL, as in the
  *      control-step state batch.  An unflagged leg reports 0.
  * No contact detection in this entry, no friction limit as a constraint (qlamd_wholebody_plant_step_friction_batch of
- * qlamd_plant_friction.h has it), no position-level drift correction: the report gives
+ * qlamd_plant_friction.h has it), no position-level drift correction
+ * (qlamd_wholebody_plant_step_anchored_batch of qlamd_contact_anchor.h has it): the report gives
  * what it takes to drop a flag -- qlamd_wholebody_contact_update_batch (qlamd_contact_detection.h) reads it and does, on the device.
  * A robot whose status is not QLAMD_STATUS_OK (a pivot not positive or a value not finite, nu+ and p included): nu as it came
  * in post_impact_velocity, zeros in impulse, contact_report, acceleration and contact_force, its state unchanged in next; or

@@ -49,7 +49,8 @@ extern "C" {
  * Refused with QLAMD_ERR_INVALID_ARGUMENT, nothing written: what the hard entry refuses; contacts == NULL; friction_coefficient
  * not finite or <= 0 (with or without a report: it is the constraint).
  * Memory spaces, streams, QLAMD_ERR_BUSY and capture as for the hard entry; next may alias the state.
- * Not built: a round cone, mu = 0, warm starts of the plant's QPs, position-level drift correction. */
+ * Position-level drift correction of a held foot is qlamd_wholebody_plant_step_anchored_batch (qlamd_contact_anchor.h, which this
+ * file includes at its end).  Not built: a round cone, mu = 0, warm starts of the plant's QPs. */
 #define QLAMD_HAS_PLANT_FRICTION 1 /* (the feature test: the version number did not move with this entry) */
 #define QLAMD_CONTACT_SEPARATING 8 /* n . f = 0 is active: the force is at the apex of its pyramid */
 #define QLAMD_CONTACT_SLIDING 16   /* a friction face is active, and the leg is not separating */
@@ -68,5 +69,9 @@ int qlamd_wholebody_plant_step_friction_batch(qlamd_context *ctx, const qlamd_wh
 #ifdef __cplusplus
 }
 #endif
+
+/* contact anchors (QLAMD_HAS_CONTACT_ANCHORS, qlamd_wholebody_plant_step_anchored_batch and
+ * qlamd_wholebody_contact_update_anchored_batch): part of this interface, kept in a file of its own that ships beside this one */
+#include "qlamd_contact_anchor.h"
 
 #endif /* QLAMD_PLANT_FRICTION_H */

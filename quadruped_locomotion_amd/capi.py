@@ -938,7 +938,8 @@ def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, st
 def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream, contacts=None):
     """contacts: None = qlamd_wholebody_forward_dynamics_batch; (entry, struct or None) = that entry -- plant_contacts.py's declared
     qlamd_wholebody_plant_step_batch -- with the struct (None: NULL) in front of `status`; (entry, struct, struct) = an entry with
-    two of them there, in that order (plant_friction.py's qlamd_wholebody_plant_step_friction_batch)."""
+    two of them there, in that order (plant_friction.py's qlamd_wholebody_plant_step_friction_batch); (entry, struct, struct, struct)
+    = three (contact_anchor.py's qlamd_wholebody_plant_step_anchored_batch)."""
     head = (ctx._h, C.byref(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B, _ptr(acc), _ptr(f),
             C.byref(nxt) if nxt is not None else None)
     if contacts is None:

@@ -31,8 +31,18 @@
    and with the random torques of the other rows, each without a touchdown and with every robot projecting, with the distribution
    of `iterations`.  Part 2 also reports the separating and sliding legs per tick and robot.
 
+6. --anchor [--position-gain KP] [--max-error E] (implies --detect; with or without --friction): the update and the plant step of
+   part 2 are qlamd_wholebody_contact_update_anchored_batch and qlamd_wholebody_plant_step_anchored_batch: the update keeps an
+   anchor per leg (with --friction a sliding foot is re-anchored), the plant step pulls each held foot to its anchor with
+   k_p = KP (1/s^2; default 0.1 / dt^2) on an error clamped to E metres (default 0.01).  The first anchors are the feet (an update
+   without flags under a rule that takes no foot).  Part 1
+   adds the three anchored kernels alone next to their parents (anchors 2 mm from the feet).  Part 2 also reports, per quarter of
+   the run: |gap| of the held feet (largest and median), their distance |p - anchor| from the anchor the tick ran with, and the
+   events per robot and tick, re-anchorings included.
+
 usage: closed_loop_probe.py [--batch 4096] [--ticks 64] [--batches 4096,65536,1048576] [--steps 64] [--repeats 5] [--out file]
-                            [--contacts] [--velocity-gain K] [--detect] [--terrain plane|heightfield] [--friction]"""
+                            [--contacts] [--velocity-gain K] [--detect] [--terrain plane|heightfield] [--friction]
+                            [--anchor] [--position-gain KP] [--max-error E]"""
 import argparse
 import os
 import sys
@@ -57,7 +67,11 @@ def main():
     ap.add_argument("--detect", action="store_true")
     ap.add_argument("--terrain", choices=("plane", "heightfield"), default="plane")
     ap.add_argument("--friction", action="store_true")
+    ap.add_argument("--anchor", action="store_true")
+    ap.add_argument("--position-gain", type=float, default=0.1 / DT ** 2)
+    ap.add_argument("--max-error", type=float, default=0.01)
     a = ap.parse_args()
+    a.detect = a.detect or a.anchor
     a.contacts = a.contacts or a.detect or a.friction
     import torch
     from quadruped_locomotion_amd import capi, plant_contacts, synth
@@ -65,6 +79,8 @@ def main():
         from quadruped_locomotion_amd import contact_detection
     if a.friction:
         from quadruped_locomotion_amd import plant_friction
+    if a.anchor:
+        from quadruped_locomotion_amd import contact_anchor
     MU = 0.6
     ctx = capi.Context(device=0)
     stream = torch.cuda.current_stream().cuda_stream
@@ -165,6 +181,32 @@ def main():
                 "%d written)   status OK %d / %d   | qlamd_wholebody_dynamics_batch %.0f GB/s of its 4464 B written + 304 B read per robot"
                 % (B, a.terrain, t_upd[0], t_upd[1], B * per / t_upd[0] * 1e-3, per, per - UPDATE_BYTES[1], UPDATE_BYTES[1],
                    int((st == 0).sum()), B, B * 4768 / t_dyn[0] * 1e-3))
+            if a.anchor:
+                anchor = f64(B, 12)
+                call = contact_anchor.AnchoredContactUpdateCall(ctx, dd, st, anchor, reanchor_mask=16, report=report, stream=stream,
+                                                                **ter, **o, **RULE)   # checked once
+                t_anc = sample(call, n)
+                del call
+                say("%8d robots: qlamd_wholebody_contact_update_anchored_batch (%s, every output) %8.2f (%.2f) = %.0f GB/s of its %d B per "
+                    "robot (up to 96 more written)   status OK %d / %d" % (B, a.terrain, t_anc[0], t_anc[1], B * (per + 96) / t_anc[0] * 1e-3,
+                                                                           per + 96, int((st == 0).sum()), B))
+                # anchors 2 mm from the feet, the plant kernels alone: hard contacts and (--friction) the cone, random torques
+                anchor.copy_(o["foot_pos"])
+                anchor += 0.002 / 3 ** 0.5
+                perr = f64(B, 12)
+                nxt2 = dict(q=f64(B, 12), qd=f64(B, 12), base_pos=f64(B, 3), base_quat=f64(B, 4), base_linvel=f64(B, 3), base_angvel=f64(B, 3))
+                kw2 = dict(acc=acc, f=f, dt=DT, next=nxt2, stream=stream, velocity_gain=a.velocity_gain, position_error=perr)
+                for cone_on in ((False, True) if a.friction else (False,)):
+                    res = []
+                    for prev in (dd["stance"], zeros):
+                        res.append(sample(contact_anchor.AnchoredPlantStepCall(ctx, d, tau, st, anchor, a.position_gain, a.max_error, friction=MU,
+                                                                               cone=cone_on, prev_stance=prev, **kw2), n))
+                        res.append(int((st == 0).sum()))
+                    say("%8d robots: qlamd_wholebody_plant_step_anchored_batch (%s), k_p %g, e_max %g, random torques: no touchdown %8.2f (%.2f) "
+                        "status OK %d / %d   every robot projecting %8.2f (%.2f) status OK %d / %d"
+                        % (B, "friction, mu %.1f" % MU if cone_on else "hard contacts", a.position_gain, a.max_error, res[0][0], res[0][1], res[1], B,
+                           res[2][0], res[2][1], res[3], B))
+                del anchor, perr, nxt2
             del dd, ter, o
         bytes_step = B * (272 + 96 + 4 + 24 + 144 + 96 + 296 + 4)
         say("%8d robots: nu' and f %8.2f (%.2f)   nu', f and next state %8.2f (%.2f) = %.0f GB/s of its %d B per robot   status OK %d / %d"
@@ -209,9 +251,18 @@ def main():
             d["normals"] = f64(B, 12)
             d["normals"].reshape(B, 4, 3)[:, :, 2] = 1.0
             prev, report, st_up, o = zero_flags.clone(), zero_flags.clone(), torch.zeros(B, dtype=torch.int32, **dev), update_outputs(B)
-            update = contact_detection.ContactUpdateCall(ctx, d, st_up, report=report, stream=stream, support_next=d["stance"],
-                                                         sensor=o["sensor"], events=o["events"], gap=o["gap"], normals=d["normals"],
-                                                         **ter, **RULE)   # checked once; the tick launches it
+            if a.anchor:
+                anchor = f64(B, 12)   # the first anchors: every foot where it is (an update without flags, under a rule that takes no foot)
+                contact_anchor.wholebody_contact_update_anchored_device(ctx, {k: v for k, v in d.items() if k != "stance"}, st_up, anchor,
+                                                                        stream=stream, approach_speed=-1e300, **ter)
+                update = contact_anchor.AnchoredContactUpdateCall(ctx, d, st_up, anchor, reanchor_mask=16 if a.friction else 0, report=report,
+                                                                  stream=stream, support_next=d["stance"], sensor=o["sensor"],
+                                                                  events=o["events"], gap=o["gap"], normals=d["normals"],
+                                                                  foot_pos=o["foot_pos"], **ter, **RULE)
+            else:
+                update = contact_detection.ContactUpdateCall(ctx, d, st_up, report=report, stream=stream, support_next=d["stance"],
+                                                             sensor=o["sensor"], events=o["events"], gap=o["gap"], normals=d["normals"],
+                                                             **ter, **RULE)   # checked once; the tick launches it
         tau, st_qp, st_pl = f64(B, 12), torch.zeros(B, dtype=torch.int32, **dev), torch.zeros(B, dtype=torch.int32, **dev)
         mem, ws = torch.zeros(B, 4, dtype=torch.int64, **dev), torch.zeros(B, dtype=torch.int64, **dev)
         prev_ws = torch.zeros_like(ws)
@@ -221,7 +272,11 @@ def main():
         def tick(k):
             if a.detect:
                 capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
-                if a.friction:
+                if a.anchor:
+                    contact_anchor.wholebody_plant_step_anchored_device(ctx, d, tau, st_pl, anchor, a.position_gain, max_error=a.max_error,
+                                                                        friction=MU, cone=a.friction, dt=DT, next=d, stream=stream,
+                                                                        velocity_gain=a.velocity_gain, prev_stance=prev, report=report)
+                elif a.friction:
                     plant_friction.wholebody_plant_step_friction_device(ctx, d, tau, st_pl, MU, dt=DT, next=d, stream=stream,
                                                                         velocity_gain=a.velocity_gain, prev_stance=prev, report=report)
                 else:
@@ -253,8 +308,16 @@ def main():
             return e0.elapsed_time(e1) * 1e3 / K
         for k in range(K):
             ran_with = d["stance"].clone() if a.detect else stance[k]
+            held_at = anchor.clone() if a.anchor else None
             tick(k)
             torch.cuda.synchronize()
+            if a.anchor:
+                on_ = ran_with != 0
+                gap_ = o["gap"][on_].abs()
+                off_ = (o["foot_pos"] - held_at).reshape(B, 4, 3).norm(dim=2)[on_]
+                gap_, off_ = gap_[torch.isfinite(gap_)], off_[torch.isfinite(off_)]
+                anchors.append((float(gap_.max()), float(gap_.median()), float(off_.max()), float(off_.median()),
+                                int((o["events"] & 8).ne(0).sum())))
             same = float((ws == prev_ws).float().mean()) if k else float("nan")
             prev_ws.copy_(ws)
             if a.detect:
@@ -268,7 +331,7 @@ def main():
                 cone.append((int((report_f & 8).ne(0).sum()), int((report_f & 16).ne(0).sum())))
         return stats
 
-    cone = []
+    cone, anchors = [], []
     stats = loop(False)
     t = [loop(True) for _ in range(a.repeats + 1)][1:]
     say("closed loop: %d trot robots, %d ticks of qlamd_wholebody_solve_placed_batch (table) -> plant step in place (%s), dt %.4f s; "
@@ -288,6 +351,17 @@ def main():
             % (np.mean([x[0] for x in disagree]), np.mean([x[0] for x in disagree[:max(1, K // 4)]]), np.mean([x[0] for x in disagree[-max(1, K // 4):]]),
                np.mean([x[1] for x in disagree]) / B, np.mean([x[2] for x in disagree]) / B, np.mean([x[3] for x in disagree]) / B,
                np.mean([x[4] for x in disagree]) / B))
+    if a.anchor:
+        say("  the update and the plant step are the anchored entries: k_p %g / s^2, e_max %g m, %s; per quarter of the run, over the feet "
+            "each tick's plant step held:" % (a.position_gain, a.max_error, "a sliding foot is re-anchored" if a.friction else "no re-anchoring"))
+        q4 = max(1, K // 4)
+        for lo in range(0, K, q4):
+            part, ev = anchors[lo:lo + q4], disagree[lo:lo + q4]
+            say("  ticks %3d-%3d: held-foot |gap| m largest %.4g, median of the ticks' medians %.4g; |p - anchor| m largest %.4g, median %.4g; per "
+                "tick and robot: touchdowns %.4f, released by the report %.4f, by the gap %.4f, re-anchored %.4f"
+                % (lo, lo + len(part) - 1, max(x[0] for x in part), float(np.median([x[1] for x in part])), max(x[2] for x in part),
+                   float(np.median([x[3] for x in part])), np.mean([x[1] for x in ev]) / B, np.mean([x[2] for x in ev]) / B,
+                   np.mean([x[3] for x in ev]) / B, np.mean([x[4] for x in part]) / B))
     say("  us per tick (%s launches): %s median %.2f spread %.2f" % ("three" if a.detect else "two", " ".join("%.2f" % x for x in t), float(np.median(t)), max(t) - min(t)))
     q = max(1, K // 4)
     for lo in range(0, K, q):
