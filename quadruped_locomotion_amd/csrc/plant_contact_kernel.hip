@@ -1,49 +1,32 @@
 // HIP kernel (gfx950) of the plant step with touchdown impacts, contact stabilisation and the contact report, and its entry of
 // the C-ABI (include/qlamd_plant_contacts.h, which qlamd.h includes).  The arithmetic is csrc/plant_contact_coop.hpp's: the KKT
-// system of plant_coop.hpp, factored once and applied twice.
-#include "plant_contact_coop.hpp"
-#include "context.hpp"
+// system of plant_coop.hpp, factored once and applied twice.  The lane layout, the failure rule, the tail and the entry's checks
+// and staging are csrc/plant_step_body.hpp's.
+#include "plant_step_body.hpp"
 
 using namespace qlamd;
 using namespace qlamd::rt;
 
 namespace {
 
-// (no __restrict__ anywhere: the next state may be written over the state it was computed from)
-struct ContactIn {
-  const double *q, *qd, *quat, *linvel, *angvel;
-  const uint8_t *stance;           // or NULL: free flight
-  const uint8_t *prev;             // or NULL: no touchdown
-  const double *normals;           // or NULL: the base's z axis
-  const double *tau, *gext, *pos;  // gext, pos: or NULL
-};
-struct ContactOut {
-  double *acc, *force;                           // or NULL
-  double *nu_plus, *impulse;                     // or NULL
-  uint8_t *report;                               // or NULL
-  double *q, *qd, *pos, *quat, *linvel, *angvel; // all NULL: no state update
-  int32_t *status;
-};
-
-// TWIN OF plant_step_kernel (plant_kernel.hip): the load prologue, the output and state-update tail, and the entry's checks and
-// staging below repeat that file's, with nu+ in the place of nu and the contact inputs and outputs added (that unit keeps its
-// text, so nothing is shared through it).  A fix to one belongs in the other.
+// TWIN OF anchored_plant_body<false> (contact_anchor_kernel.hip), which adds the anchors, and in its load prologue of
+// plant_step_kernel (plant_kernel.hip): from the prologue to the status this stays text of each kernel, because the compiler pairs
+// multiplications and additions differently once the same text stands in a function that several kernels call, and the results
+// move in their last bits (profiles/r17/refactor_checks.md).  A fix to one belongs in the others.
 // One robot per 16-lane row.  Everything is loaded before the first use and stored after the last: the outputs may alias the inputs.
 // Robots with and without a touchdown share wavefronts: a robot without one runs the impact with a zero right-hand side and keeps
 // its velocity by a select.
-__global__ __launch_bounds__(64) void plant_contact_kernel(const DeviceParams *Pp, const coop::WbParamsDev W, const ContactIn s, int64_t B,
-                                                           double dt, double kv, double mu, const ContactOut o) {
+__global__ __launch_bounds__(64) void plant_contact_kernel(const DeviceParams *Pp, const coop::WbParamsDev W, const PlantContactIn s,
+                                                           int64_t B, double dt, double kv, double mu, const PlantContactOut o) {
   using namespace coop;
   __shared__ double tab[4 * kTabPerLeg];
   const DeviceParams &P = *Pp;
   TabStage ts;
   ts.issue(P);
-  const int row = threadIdx.x >> 4, lr = threadIdx.x & 15, leg = lr >> 2, c = lr & 3;
-  const int64_t i0 = (int64_t)blockIdx.x * 4 + row;
-  const bool live = i0 < B;
-  const int64_t i = live ? i0 : B - 1;
-  const bool comp = c < 3;
-  const int jq = 3 * leg + (comp ? c : 2);
+  const PlantLane ln = plant_lane(B);
+  const int lr = ln.lr, leg = ln.leg, c = ln.c, jq = ln.jq;
+  const int64_t i = ln.i;
+  const bool comp = ln.comp;
   const bool step = o.q != nullptr;
   double quat[4], linvel[3], angvel[3], pos[3] = {0.0, 0.0, 0.0}, ge[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   {
@@ -124,20 +107,9 @@ __global__ __launch_bounds__(64) void plant_contact_kernel(const DeviceParams *P
   const double f = x.y;
   const bool ok = !row_any(!(F.ok && plant_applied_finite(imp, comp) && plant_applied_finite(x, comp)));
 
-  // ---- outputs.  A failed robot: zeros, nu and its state as they came, or (QLAMD_ON_FAILURE_KEEP) nothing but its status
-  if (lr == 0 && live) o.status[i] = ok ? kStatusOk : kStatusNotPd;
-  if (!live || (!ok && P.keep_on_failure)) return;
+  // ---- outputs.  A failed robot's nu+ is nu as it came
+  if (!plant_store_status(o.status, ln, ok ? kStatusOk : kStatusNotPd, P)) return;
   const int64_t jo = 3 * leg + c; // my joint / my force component (lanes c < 3)
-  if (o.acc) {
-    if (comp) o.acc[18 * i + 6 + jo] = ok ? x.xj : 0.0;
-    if (lr < 6) {
-      double v = x.xb[0];
-#pragma unroll
-      for (int b = 1; b < 6; b++) v = sel(lr == b, x.xb[b], v);
-      o.acc[18 * i + lr] = ok ? v : 0.0;
-    }
-  }
-  if (o.force && comp) o.force[12 * i + jo] = ok ? f : 0.0;
   if (o.nu_plus) {
     if (comp) o.nu_plus[18 * i + 6 + jo] = ok ? qdp : qdj;
     if (lr < 6) {
@@ -155,36 +127,7 @@ __global__ __launch_bounds__(64) void plant_contact_kernel(const DeviceParams *P
     const unsigned bits = plant_contact_bits(fl, nB, mu) | (((touch >> leg) & 1u) ? 4u : 0u);
     if (c == 0) o.report[4 * i + leg] = (uint8_t)((ok && on) ? bits : 0u);
   }
-  if (!step) return;
-  // semi-implicit Euler from nu+ (include/qlamd.h has the rule)
-  double qn[4] = {quat[0], quat[1], quat[2], quat[3]}, pn[3] = {pos[0], pos[1], pos[2]};
-  double ln[3] = {linvel[0], linvel[1], linvel[2]}, wn[3] = {angvel[0], angvel[1], angvel[2]};
-  double qdn = qdj, qjn = qj;
-  if (ok) {
-    qdn = qdp + dt * x.xj;
-    qjn = qj + dt * qdn;
-    double vn[3], phi[3], dv[3], Rn[9];
-#pragma unroll
-    for (int a = 0; a < 3; a++) { vn[a] = nup[a] + dt * x.xb[a]; wn[a] = nup[3 + a] + dt * x.xb[3 + a]; phi[a] = dt * wn[a]; }
-    plant_quat_step(quat, phi, qn);
-    rot(Rm, vn, dv);
-#pragma unroll
-    for (int a = 0; a < 3; a++) pn[a] = pos[a] + dt * dv[a];
-    quat_to_matrix(qn, Rn);
-    rot(Rn, vn, ln);
-  }
-  if (comp) { o.q[12 * i + jo] = qjn; o.qd[12 * i + jo] = qdn; }
-  if (lr < 4) {
-    double v = qn[0];
-#pragma unroll
-    for (int b = 1; b < 4; b++) v = sel(lr == b, qn[b], v);
-    o.quat[4 * i + lr] = v;
-  }
-  if (lr < 3) {
-    o.pos[3 * i + lr] = sel(lr == 2, pn[2], sel(lr == 1, pn[1], pn[0]));
-    o.linvel[3 * i + lr] = sel(lr == 2, ln[2], sel(lr == 1, ln[1], ln[0]));
-    o.angvel[3 * i + lr] = sel(lr == 2, wn[2], sel(lr == 1, wn[1], wn[0]));
-  }
+  plant_store_tail(o, ln, quat, linvel, angvel, pos, qj, qdj, Rm, ok, dt, nup, qdp, x.xb, x.xj, f);
 }
 
 } // namespace
@@ -198,51 +141,21 @@ int qlamd_wholebody_plant_step_batch(qlamd_context *ctx, const qlamd_wholebody_b
   if (!contacts)
     return qlamd_wholebody_forward_dynamics_batch(ctx, in, joint_effort, generalized_force, base_position, gravity, dt, batch,
                                                   acceleration, contact_force, next, status, memory, stream);
-  if (!ctx || !in || batch < 0 || !joint_effort || !status) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (!in->joint_position || !in->joint_velocity || !in->base_orientation || !in->base_linear_velocity ||
-      !in->base_angular_velocity)
-    return QLAMD_ERR_INVALID_ARGUMENT;
-  if (next) {
-    if (!base_position || !(dt > 0.0) || !(dt - dt == 0.0)) return QLAMD_ERR_INVALID_ARGUMENT;
-    if (!next->joint_position || !next->joint_velocity || !next->base_position || !next->base_orientation ||
-        !next->base_linear_velocity || !next->base_angular_velocity)
-      return QLAMD_ERR_INVALID_ARGUMENT;
-  }
+  if (const int rc = plant_check(ctx, in, joint_effort, base_position, false, dt, batch, next, status, memory)) return rc;
   const double kv = contacts->velocity_gain, mu = contacts->friction_coefficient;
   if (!(kv >= 0.0) || !(kv - kv == 0.0)) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (contacts->contact_report && (!(mu >= 0.0) || !(mu - mu == 0.0))) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (memory != QLAMD_MEM_DEVICE && memory != QLAMD_MEM_HOST) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (contacts->contact_report && (!(mu >= 0.0) || !(mu - mu == 0.0))) return QLAMD_ERR_INVALID_ARGUMENT; // (read for the report only)
   if (batch == 0) return QLAMD_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
-  const size_t B = (size_t)batch;
-  ContactIn s{in->joint_position, in->joint_velocity, in->base_orientation, in->base_linear_velocity, in->base_angular_velocity,
-              in->support_leg, contacts->previous_support_leg, in->surface_normal, joint_effort, generalized_force,
-              next ? base_position : nullptr};
-  ContactOut o{};
-  o.acc = acceleration; o.force = contact_force; o.status = status;
-  o.nu_plus = contacts->post_impact_velocity; o.impulse = contacts->impulse; o.report = contacts->contact_report;
-  if (next) {
-    o.q = next->joint_position; o.qd = next->joint_velocity; o.pos = next->base_position; o.quat = next->base_orientation;
-    o.linvel = next->base_linear_velocity; o.angvel = next->base_angular_velocity;
-  }
-  const bool keep = ctx->params.keep_on_failure != 0; // entries the kernel leaves alone come back as they went up
+  PlantCall k = plant_call(in, joint_effort, generalized_force, next ? base_position : nullptr, acceleration, contact_force, next,
+                           contacts, status);
   Staged sg(memory == QLAMD_MEM_HOST);
-  sg.in(s.q, B * 96); sg.in(s.qd, B * 96); sg.in(s.quat, B * 32); sg.in(s.linvel, B * 24); sg.in(s.angvel, B * 24);
-  sg.in(s.stance, B * 4); sg.in(s.prev, B * 4); sg.in(s.normals, B * 96); sg.in(s.tau, B * 96); sg.in(s.gext, B * 144);
-  sg.in(s.pos, B * 24);
-  sg.out(o.acc, B * 144, keep); sg.out(o.force, B * 96, keep);
-  sg.out(o.nu_plus, B * 144, keep); sg.out(o.impulse, B * 96, keep); sg.out(o.report, B * 4, keep);
-  sg.out(o.q, B * 96, keep); sg.out(o.qd, B * 96, keep); sg.out(o.pos, B * 24, keep); sg.out(o.quat, B * 32, keep);
-  sg.out(o.linvel, B * 24, keep); sg.out(o.angvel, B * 24, keep); sg.out(o.status, B * 4);
+  plant_stage(sg, k, (size_t)batch, ctx->params.keep_on_failure != 0);
   if (const int rc = sg.upload(ctx, st)) return rc;
-  coop::WbParamsDev W;
-  W.base_m = ctx->base_m;
-  for (int a = 0; a < 3; a++) W.base_h[a] = ctx->base_h[a];
-  for (int a = 0; a < 6; a++) W.base_I[a] = ctx->base_I[a];
-  W.w_tau = 0.0; W.tau_max = 0.0; W.grav = gravity;
-  hipLaunchKernelGGL(plant_contact_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, st, ctx->d_params, W, s, batch, dt, kv, mu, o);
+  hipLaunchKernelGGL(plant_contact_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, st, ctx->d_params, plant_params(ctx, gravity),
+                     static_cast<const PlantContactIn &>(k.s), batch, dt, kv, mu, static_cast<const PlantContactOut &>(k.o));
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   return sg.finish(st);
 }

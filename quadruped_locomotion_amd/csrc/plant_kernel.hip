@@ -1,26 +1,18 @@
 // HIP kernel (gfx950) of the whole-body plant step -- contact-constrained forward dynamics and the state update -- and its
-// entry of the C-ABI of include/qlamd.h.  The arithmetic is csrc/plant_coop.hpp's.
-#include "plant_coop.hpp"
-#include "context.hpp"
+// entry of the C-ABI of include/qlamd.h.  The arithmetic is csrc/plant_coop.hpp's; the lane layout, the failure rule, the tail
+// and the entry's checks and staging are csrc/plant_step_body.hpp's, shared with the plant steps with contacts.
+#include "plant_step_body.hpp"
 
 using namespace qlamd;
 using namespace qlamd::rt;
 
 namespace {
 
-// (no __restrict__ anywhere: the next state may be written over the state it was computed from)
-struct PlantIn {
-  const double *q, *qd, *quat, *linvel, *angvel;
-  const uint8_t *stance;           // or NULL: free flight
-  const double *tau, *gext, *pos;  // gext, pos: or NULL
-};
-struct PlantOut {
-  double *acc, *force;                          // or NULL
-  double *q, *qd, *pos, *quat, *linvel, *angvel; // all NULL: accelerations only
-  int32_t *status;
-};
-
 // One robot per 16-lane row.  Everything is loaded before the first use and stored after the last: the outputs may alias the inputs.
+// TWIN OF the load prologues of plant_contact_kernel (plant_contact_kernel.hip), plant_friction_kernel (plant_friction_kernel.hip) and
+// anchored_plant_body (contact_anchor_kernel.hip), which add their own loads: the prologue stays text of each kernel because the
+// compiler pairs multiplications and additions downstream of it differently once the loads come out of a function of their own
+// (profiles/r17/refactor_checks.md).  A fix to one belongs in the others.
 __global__ __launch_bounds__(64) void plant_step_kernel(const DeviceParams *Pp, const coop::WbParamsDev W, const PlantIn s, int64_t B,
                                                         double dt, const PlantOut o) {
   using namespace coop;
@@ -28,12 +20,10 @@ __global__ __launch_bounds__(64) void plant_step_kernel(const DeviceParams *Pp, 
   const DeviceParams &P = *Pp;
   TabStage ts;
   ts.issue(P);
-  const int row = threadIdx.x >> 4, lr = threadIdx.x & 15, leg = lr >> 2, c = lr & 3;
-  const int64_t i0 = (int64_t)blockIdx.x * 4 + row;
-  const bool live = i0 < B;
-  const int64_t i = live ? i0 : B - 1;
-  const bool comp = c < 3;
-  const int jq = 3 * leg + (comp ? c : 2);
+  const PlantLane ln = plant_lane(B);
+  const int leg = ln.leg, c = ln.c, jq = ln.jq;
+  const int64_t i = ln.i;
+  const bool comp = ln.comp;
   const bool step = o.q != nullptr;
   double quat[4], linvel[3], angvel[3], pos[3] = {0.0, 0.0, 0.0}, ge[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   {
@@ -80,51 +70,10 @@ __global__ __launch_bounds__(64) void plant_step_kernel(const DeviceParams *Pp, 
   PlantSolution x;
   plant_solve(L, leg, c, T, Fcol, Mleg, hb, hj, gam, ge, comp ? tauj + gej : 0.0, on, x);
 
-  // ---- outputs.  A failed robot: zeros and its state as it came, or (QLAMD_ON_FAILURE_KEEP) nothing but its status
-  const bool ok = x.ok;
-  if (lr == 0 && live) o.status[i] = ok ? kStatusOk : kStatusNotPd;
-  if (!live || (!ok && P.keep_on_failure)) return;
-  if (o.acc) {
-    if (comp) o.acc[18 * i + 6 + 3 * leg + c] = ok ? x.nuj : 0.0;
-    if (lr < 6) {
-      double v = x.nub[0];
-#pragma unroll
-      for (int b = 1; b < 6; b++) v = sel(lr == b, x.nub[b], v);
-      o.acc[18 * i + lr] = ok ? v : 0.0;
-    }
-  }
-  if (o.force && comp) o.force[12 * i + 3 * leg + c] = ok ? x.f : 0.0;
-  if (!step) return;
-  // semi-implicit Euler: nu+ = nu + dt nu', q+ = q + dt qd+, quat+ = normalise(quat (x) exp(dt w+)), pos+ = pos + dt R(quat) v+,
-  // world linear velocity+ = R(quat+) v+
-  double qn[4] = {quat[0], quat[1], quat[2], quat[3]}, pn[3] = {pos[0], pos[1], pos[2]};
-  double ln[3] = {linvel[0], linvel[1], linvel[2]}, wn[3] = {angvel[0], angvel[1], angvel[2]};
-  double qdn = qdj, qjn = qj;
-  if (ok) {
-    qdn = qdj + dt * x.nuj;
-    qjn = qj + dt * qdn;
-    double vn[3], phi[3], dv[3], Rn[9];
-#pragma unroll
-    for (int a = 0; a < 3; a++) { vn[a] = vB[a] + dt * x.nub[a]; wn[a] = angvel[a] + dt * x.nub[3 + a]; phi[a] = dt * wn[a]; }
-    plant_quat_step(quat, phi, qn);
-    rot(Rm, vn, dv);
-#pragma unroll
-    for (int a = 0; a < 3; a++) pn[a] = pos[a] + dt * dv[a];
-    quat_to_matrix(qn, Rn);
-    rot(Rn, vn, ln);
-  }
-  if (comp) { o.q[12 * i + 3 * leg + c] = qjn; o.qd[12 * i + 3 * leg + c] = qdn; }
-  if (lr < 4) {
-    double v = qn[0];
-#pragma unroll
-    for (int b = 1; b < 4; b++) v = sel(lr == b, qn[b], v);
-    o.quat[4 * i + lr] = v;
-  }
-  if (lr < 3) {
-    o.pos[3 * i + lr] = sel(lr == 2, pn[2], sel(lr == 1, pn[1], pn[0]));
-    o.linvel[3 * i + lr] = sel(lr == 2, ln[2], sel(lr == 1, ln[1], ln[0]));
-    o.angvel[3 * i + lr] = sel(lr == 2, wn[2], sel(lr == 1, wn[1], wn[0]));
-  }
+  // ---- outputs, and the state integrated from nu
+  if (!plant_store_status(o.status, ln, x.ok ? kStatusOk : kStatusNotPd, P)) return;
+  const double nu[6] = {vB[0], vB[1], vB[2], angvel[0], angvel[1], angvel[2]};
+  plant_store_tail(o, ln, quat, linvel, angvel, pos, qj, qdj, Rm, x.ok, dt, nu, qdj, x.nub, x.nuj, x.f);
 }
 
 } // namespace
@@ -135,44 +84,21 @@ int qlamd_wholebody_forward_dynamics_batch(qlamd_context *ctx, const qlamd_whole
                                            const double *generalized_force, const double *base_position, double gravity, double dt,
                                            int64_t batch, double *acceleration, double *contact_force, const qlamd_plant_next *next,
                                            int32_t *status, int memory, void *stream) {
-  if (!ctx || !in || batch < 0 || !joint_effort || !status) return QLAMD_ERR_INVALID_ARGUMENT;
-  if (!in->joint_position || !in->joint_velocity || !in->base_orientation || !in->base_linear_velocity ||
-      !in->base_angular_velocity)
-    return QLAMD_ERR_INVALID_ARGUMENT;
-  if (next) {
-    if (!base_position || !(dt > 0.0) || !(dt - dt == 0.0)) return QLAMD_ERR_INVALID_ARGUMENT;
-    if (!next->joint_position || !next->joint_velocity || !next->base_position || !next->base_orientation ||
-        !next->base_linear_velocity || !next->base_angular_velocity)
-      return QLAMD_ERR_INVALID_ARGUMENT;
-  }
-  if (memory != QLAMD_MEM_DEVICE && memory != QLAMD_MEM_HOST) return QLAMD_ERR_INVALID_ARGUMENT;
+  if (const int rc = plant_check(ctx, in, joint_effort, base_position, false, dt, batch, next, status, memory)) return rc;
   if (batch == 0) return QLAMD_OK;
   if (hipSetDevice(ctx->device) != hipSuccess) return QLAMD_ERR_HIP;
   hipStream_t st = (hipStream_t)stream;
   QL_ENTER(ctx, st);
-  const size_t B = (size_t)batch;
-  PlantIn s{in->joint_position, in->joint_velocity, in->base_orientation, in->base_linear_velocity, in->base_angular_velocity,
-            in->support_leg, joint_effort, generalized_force, next ? base_position : nullptr};
-  PlantOut o{};
-  o.acc = acceleration; o.force = contact_force; o.status = status;
-  if (next) {
-    o.q = next->joint_position; o.qd = next->joint_velocity; o.pos = next->base_position; o.quat = next->base_orientation;
-    o.linvel = next->base_linear_velocity; o.angvel = next->base_angular_velocity;
-  }
-  const bool keep = ctx->params.keep_on_failure != 0; // entries the kernel leaves alone come back as they went up
+  PlantCall k = plant_call(in, joint_effort, generalized_force, next ? base_position : nullptr, acceleration, contact_force, next,
+                           nullptr, status);
   Staged sg(memory == QLAMD_MEM_HOST);
-  sg.in(s.q, B * 96); sg.in(s.qd, B * 96); sg.in(s.quat, B * 32); sg.in(s.linvel, B * 24); sg.in(s.angvel, B * 24);
-  sg.in(s.stance, B * 4); sg.in(s.tau, B * 96); sg.in(s.gext, B * 144); sg.in(s.pos, B * 24);
-  sg.out(o.acc, B * 144, keep); sg.out(o.force, B * 96, keep);
-  sg.out(o.q, B * 96, keep); sg.out(o.qd, B * 96, keep); sg.out(o.pos, B * 24, keep); sg.out(o.quat, B * 32, keep);
-  sg.out(o.linvel, B * 24, keep); sg.out(o.angvel, B * 24, keep); sg.out(o.status, B * 4);
+  plant_stage(sg, k, (size_t)batch, ctx->params.keep_on_failure != 0);
   if (const int rc = sg.upload(ctx, st)) return rc;
-  coop::WbParamsDev W;
-  W.base_m = ctx->base_m;
-  for (int a = 0; a < 3; a++) W.base_h[a] = ctx->base_h[a];
-  for (int a = 0; a < 6; a++) W.base_I[a] = ctx->base_I[a];
-  W.w_tau = 0.0; W.tau_max = 0.0; W.grav = gravity;
-  hipLaunchKernelGGL(plant_step_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, st, ctx->d_params, W, s, batch, dt, o);
+  // (this kernel's arguments have no room for the contact arrays, which are NULL here)
+  const PlantIn s{k.s.q, k.s.qd, k.s.quat, k.s.linvel, k.s.angvel, k.s.stance, k.s.tau, k.s.gext, k.s.pos};
+  const PlantOut o{k.o.acc, k.o.force, k.o.q, k.o.qd, k.o.pos, k.o.quat, k.o.linvel, k.o.angvel, k.o.status};
+  hipLaunchKernelGGL(plant_step_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, st, ctx->d_params, plant_params(ctx, gravity),
+                     s, batch, dt, o);
   if (hipGetLastError() != hipSuccess) return QLAMD_ERR_HIP;
   return sg.finish(st);
 }
