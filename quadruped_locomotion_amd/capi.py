@@ -286,6 +286,16 @@ def lib():
     return _lib
 
 
+def declared(signatures):
+    """lib() with the entries of an extension header's table (the SIGNATURES of plant_contacts.py, contact_detection.py, ...)
+    declared: the lib() of those modules.  A library without one of them is an error here (there is no fallback)."""
+    L = lib()
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
 # ---- one helper per marshalling job ------------------------------------------------------------------------------------------
 def _call(fn, *args):
     """Call an entry that returns a QLAMD_* code: anything but OK raises QlamdError under the entry's own name."""
@@ -935,22 +945,18 @@ def wholebody_solve_placed_device(ctx, dstate, tau, grf, status, params=None, st
           _ptr(set_memory), tau.data_ptr(), _ptr(grf), status.data_ptr(), MEM_DEVICE, _stream(stream))
 
 
-def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream, contacts=None):
-    """contacts: None = qlamd_wholebody_forward_dynamics_batch; (entry, struct or None) = that entry -- plant_contacts.py's declared
-    qlamd_wholebody_plant_step_batch -- with the struct (None: NULL) in front of `status`; (entry, struct, struct) = an entry with
-    two of them there, in that order (plant_friction.py's qlamd_wholebody_plant_step_friction_batch); (entry, struct, struct, struct)
-    = three (contact_anchor.py's qlamd_wholebody_plant_step_anchored_batch)."""
-    head = (ctx._h, C.byref(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B, _ptr(acc), _ptr(f),
-            C.byref(nxt) if nxt is not None else None)
-    if contacts is None:
-        _call(lib().qlamd_wholebody_forward_dynamics_batch, *head, _ptr(status), memory, _stream(stream))
-    else:
-        entry, *structs = contacts
-        _call(entry, *head, *[C.byref(struct) if struct is not None else None for struct in structs], _ptr(status), memory, _stream(stream))
+def _plant_call(ctx, wb, B, tau, g_ext, base_pos, gravity, dt, acc, f, nxt, status, memory, stream, entry, *structs):
+    """One call of a plant entry: the eleven arguments every plant entry begins with, the entry's own optional structs (zero to
+    three; None: NULL) in front of `status`, and the three every entry ends with.  `entry` is a declared function of the library."""
+    _call(entry, ctx._h, C.byref(wb), _ptr(tau), _ptr(g_ext), _ptr(base_pos), gravity, dt, B, _ptr(acc), _ptr(f),
+          C.byref(nxt) if nxt is not None else None, *[C.byref(struct) if struct is not None else None for struct in structs],
+          _ptr(status), memory, _stream(stream))
 
 
-def _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, contacts=None, extra=None):
-    """The host form of both plant entries (contacts as _plant_call's) -> dict with acc, f, status, `next` with dt, and `extra`."""
+def _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, entry, structs=(), extra=None, pos_always=False):
+    """The host form of every plant entry (entry, structs: _plant_call's) -> dict with acc, f, status, `next` with dt, and `extra`.
+    base_pos goes over with dt only, unless the entry reads it in any case (pos_always, as plant_check's in
+    csrc/plant_step_body.hpp); in_place: it is the state's own array."""
     keep = []
     B = state["q"].shape[0]
     if in_place:
@@ -967,13 +973,13 @@ def _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, cont
         raise ValueError("tau must be [%d, 12] and g_ext [%d, 18]" % (B, B))
     out = dict(acc=np.zeros((B, 18)), f=np.zeros((B, 12)), status=np.full(B, -1, np.int32))
     out.update(extra or {})
-    nxt, pos = None, None
+    nxt = None
+    pos = np.ascontiguousarray(state["base_pos"], dtype=np.float64) if dt is not None or pos_always else None
     if dt is not None:
-        pos = np.ascontiguousarray(state["base_pos"], dtype=np.float64)
         out["next"] = {key: (state[key] if in_place else np.zeros((B, n))) for _, key, n in PLANT_NEXT_FIELDS}
         nxt = PlantNext(*[_ptr(out["next"][key]) for _, key, _ in PLANT_NEXT_FIELDS])
     _plant_call(ctx, wb, B, tau, g_ext, pos, float(gravity), float(dt) if dt is not None else 0.0, out["acc"], out["f"], nxt,
-                out["status"], MEM_HOST, None, contacts)
+                out["status"], MEM_HOST, None, entry, *structs)
     return out
 
 
@@ -981,24 +987,31 @@ def wholebody_forward_dynamics(ctx, state, tau, g_ext=None, gravity=9.81, dt=Non
     """qlamd_wholebody_forward_dynamics_batch on host buffers -> dict with acc [B,18], f [B,12], status [B] and, with dt, `next`:
     the state after dt under the keys of `state` (q, qd, base_pos, base_quat, base_linvel, base_angvel).  state["stance"] flags the
     held feet (free_flight: support_leg = NULL); in_place: the next state is written over `state`'s own arrays."""
-    return _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place)
+    return _plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, lib().qlamd_wholebody_forward_dynamics_batch)
 
 
-def _plant_device(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream, contacts=None):
-    """The device form of both plant entries (contacts as _plant_call's)."""
+def _plant_device_args(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream, entry, structs=(),
+                       pos_always=False):
+    """_plant_call's arguments for the device form of every plant entry: marshalled once, they are what a kept call launches
+    again.  They hold the structs; the tensors behind the structs' pointers are the caller's to keep.  base_pos goes over with
+    `next` only, unless the entry reads it in any case (pos_always: dstate then needs it)."""
+    B = dstate["q"].shape[0]
+    if pos_always and (dstate.get("base_pos") is None or not _is(dstate["base_pos"], "float64", 3 * B)):
+        raise ValueError("dstate['base_pos'] must be a contiguous float64 tensor of %d x 3 elements: this entry always reads it" % B)
     wb = _wholebody_batch(dstate, [])
     if free_flight:
         wb.support_leg = None
     nxt = None if next is None else PlantNext(*[_ptr(next[key]) for _, key, _ in PLANT_NEXT_FIELDS])
-    _plant_call(ctx, wb, dstate["q"].shape[0], tau, g_ext, dstate.get("base_pos") if next is not None else None, float(gravity),
-                float(dt), acc, f, nxt, status, MEM_DEVICE, stream, contacts)
+    return (ctx, wb, B, tau, g_ext, dstate.get("base_pos") if next is not None or pos_always else None, float(gravity), float(dt),
+            acc, f, nxt, status, MEM_DEVICE, stream, entry, *structs)
 
 
 def wholebody_forward_dynamics_device(ctx, dstate, tau, status, acc=None, f=None, g_ext=None, gravity=9.81, dt=0.0, next=None,
                                       free_flight=False, stream=None):
     """Same entry on torch CUDA tensors; asynchronous.  next: dict of tensors under the state's keys (q, qd, base_pos, base_quat,
     base_linvel, base_angvel) or NULL; it may be `dstate` itself, which then needs "base_pos" (a rollout in place)."""
-    _plant_device(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream)
+    _plant_call(*_plant_device_args(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream,
+                                    lib().qlamd_wholebody_forward_dynamics_batch))
 
 
 def full_tick(ctx, io, period, index_quirk=1, params=None, pid=None, memory=MEM_HOST, stream=None):

@@ -1,6 +1,7 @@
 """ctypes binding of include/qlamd_contact_detection.h (the part of the C-ABI that qlamd.h includes at its end, behind
 qlamd_plant_contacts.h) -- ground contact detection for the plant: foot positions and velocities in the world, a terrain, the next
-tick's support flags -- on the marshalling helpers of capi.py.  Plumbing only.
+tick's support flags -- on the marshalling helpers of capi.py.  Plumbing only.  Its host marshalling (_host_update) and its kept
+call (ContactUpdateCall) are contact_anchor.py's as well, whose entry takes one more struct.
 
 The same layout as capi.py: the header's constants, its structs, its functions (SIGNATURES), the wrappers.
 tests/test_contact_update_cpu.py holds all of them against the header and the C compiler."""
@@ -47,11 +48,7 @@ RULE = ("release_mask", "touchdown_distance", "approach_speed", "liftoff_distanc
 
 def lib():
     """capi.lib() with this header's entries declared; a library without them is an error here (there is no fallback)."""
-    L = capi.lib()
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return L
+    return capi.declared(SIGNATURES)
 
 
 def default_update():
@@ -90,13 +87,9 @@ def _update(B, plane, hf, report, rule, outputs):
     return u, [hf]
 
 
-def wholebody_contact_update(ctx, state, plane=None, hf=None, report=None, want=tuple(k for k, _, _, _ in OUTPUTS), in_place=False,
-                             **rule):
-    """qlamd_wholebody_contact_update_batch on host arrays.  state: q, qd [B,12], base_quat [B,4], base_linvel, base_angvel,
-    base_pos [B,3] and, optionally, stance uint8 [B,4] (the current flags; absent: none flagged).  plane [B,4] or hf (heightfield())
-    or neither (z = 0); report uint8 [B,4] or None; rule: release_mask, touchdown_distance, approach_speed, liftoff_distance,
-    sensor_distance.  -> dict with status [B] and what `want` names: support_next, sensor, events uint8 [B,4], gap [B,4], normals,
-    foot_pos, foot_vel [B,12].  in_place: support_next is state["stance"] itself."""
+def _host_update(ctx, entry, anchors, state, plane, hf, report, want, in_place, rule):
+    """The host form of both update entries: `entry` with the structs of `anchors` (none for this header's entry; one, or None for
+    NULL, for contact_anchor.py's) between the update struct and the batch size."""
     B = state["q"].shape[0]
     keep = []
     st = {k: np.ascontiguousarray(state[k], dtype=np.float64) for k, _ in STATE_KEYS}
@@ -117,16 +110,31 @@ def wholebody_contact_update(ctx, state, plane=None, hf=None, report=None, want=
         out["support_next"] = st["stance"]
     out["status"] = np.full(B, -1, np.int32)
     u, alive = _update(B, plane, hf, report, rule, out)
-    capi._call(lib().qlamd_wholebody_contact_update_batch, ctx._h, C.byref(wb), capi._ptr(st["base_pos"]), C.byref(u), B,
-               capi._ptr(out["status"]), capi.MEM_HOST, None)
+    capi._call(entry, ctx._h, C.byref(wb), capi._ptr(st["base_pos"]), C.byref(u), *[C.byref(a) if a is not None else None for a in anchors],
+               B, capi._ptr(out["status"]), capi.MEM_HOST, None)
     del alive
     return out
+
+
+def wholebody_contact_update(ctx, state, plane=None, hf=None, report=None, want=tuple(k for k, _, _, _ in OUTPUTS), in_place=False,
+                             **rule):
+    """qlamd_wholebody_contact_update_batch on host arrays.  state: q, qd [B,12], base_quat [B,4], base_linvel, base_angvel,
+    base_pos [B,3] and, optionally, stance uint8 [B,4] (the current flags; absent: none flagged).  plane [B,4] or hf (heightfield())
+    or neither (z = 0); report uint8 [B,4] or None; rule: release_mask, touchdown_distance, approach_speed, liftoff_distance,
+    sensor_distance.  -> dict with status [B] and what `want` names: support_next, sensor, events uint8 [B,4], gap [B,4], normals,
+    foot_pos, foot_vel [B,12].  in_place: support_next is state["stance"] itself."""
+    return _host_update(ctx, lib().qlamd_wholebody_contact_update_batch, (), state, plane, hf, report, want, in_place, rule)
 
 
 class ContactUpdateCall:
     """One checked device call of qlamd_wholebody_contact_update_batch, kept: calling it launches again on the same tensors with
     nothing re-checked or re-marshalled -- what a loop over ticks or a graph capture wants (the checks of
-    wholebody_contact_update_device cost more host time than the launch).  Holds every tensor and struct it points to."""
+    wholebody_contact_update_device cost more host time than the launch).  Holds every tensor and struct it points to.
+    (contact_anchor.AnchoredContactUpdateCall is this class with its own `_entry` and one struct in `_anchors`.)"""
+    _anchors = ()                                               # the structs between the update struct and the batch size
+
+    def _entry(self):
+        return lib().qlamd_wholebody_contact_update_batch
 
     def __init__(self, ctx, dstate, status, plane=None, hf=None, report=None, stream=None, support_next=None, sensor=None, events=None,
                  gap=None, normals=None, foot_pos=None, foot_vel=None, **rule):
@@ -143,9 +151,10 @@ class ContactUpdateCall:
         self._wb = capi._wholebody_batch({k: dstate.get(k) for k in [k for k, _ in STATE_KEYS[:5]] + ["stance"]}, [])
         self._update, _ = _update(B, plane, hf, report, rule, outputs)
         self._alive = (dict(dstate), status, plane, hf, report, outputs)
-        self._args = (ctx._h, C.byref(self._wb), capi._ptr(dstate["base_pos"]), C.byref(self._update), B, capi._ptr(status),
-                      capi.MEM_DEVICE, capi._stream(stream))
-        self._fn = lib().qlamd_wholebody_contact_update_batch
+        self._args = (ctx._h, C.byref(self._wb), capi._ptr(dstate["base_pos"]), C.byref(self._update),
+                      *[C.byref(a) if a is not None else None for a in self._anchors], B, capi._ptr(status), capi.MEM_DEVICE,
+                      capi._stream(stream))
+        self._fn = self._entry()
 
     def __call__(self):
         capi._call(self._fn, *self._args)

@@ -31,9 +31,7 @@ struct ContactAnchors {
 inline int detect_contacts_anchored(qlamd_context *ctx, PlantState &s, const ContactDetector &d, ContactAnchors &a,
                                     const uint8_t *contact_report, int32_t *status) {
   const qlamd_wholebody_batch in = s.batch();
-  qlamd_contact_update u = d.update;
-  u.contact_report = contact_report;
-  u.support_next = s.support_leg.data();
+  const qlamd_contact_update u = contact_update(s, d, contact_report);
   qlamd_contact_anchors ca{};
   ca.anchor = a.anchor.data();
   ca.reanchor_mask = a.reanchor_mask;
@@ -66,18 +64,8 @@ inline int step_anchored(qlamd_context *ctx, PlantState &s, const ContactAnchors
                          uint8_t *contact_report = nullptr, double *position_error = nullptr, int32_t *iterations = nullptr,
                          const double *generalized_force = nullptr) {
   const qlamd_wholebody_batch in = s.batch();
-  qlamd_plant_next next;
-  next.joint_position = s.joint_position.data();
-  next.joint_velocity = s.joint_velocity.data();
-  next.base_position = s.base_position.data();
-  next.base_orientation = s.base_orientation.data();
-  next.base_linear_velocity = s.base_linear_velocity.data();
-  next.base_angular_velocity = s.base_angular_velocity.data();
-  qlamd_plant_contacts contacts{};
-  contacts.previous_support_leg = s.previous_support_leg.data();
-  contacts.velocity_gain = k_v;
-  contacts.friction_coefficient = friction;
-  contacts.contact_report = contact_report;
+  const qlamd_plant_next next = s.next();
+  const qlamd_plant_contacts contacts = plant_contacts(s, k_v, friction, contact_report);
   qlamd_plant_friction fr{};
   fr.iterations = iterations;
   qlamd_plant_anchor pa{};

@@ -20,15 +20,21 @@ struct ContactDetector {
   qlamd_contact_update update;
 };
 
+// d.update for one call on `s`: with that plant step's report (or NULL), the next flags written over the state's own
+inline qlamd_contact_update contact_update(PlantState &s, const ContactDetector &d, const uint8_t *contact_report) {
+  qlamd_contact_update u = d.update;
+  u.contact_report = contact_report;
+  u.support_next = s.support_leg.data();
+  return u;
+}
+
 // The flags of the next step from the state `s` as the plant left it, in place: s.support_leg holds the flags the plant ran with
 // when the call is made and the next step's flags after a call that returns QLAMD_OK.  (step_with_contacts() has copied the
 // flags it ran with to s.previous_support_leg already, which is what the next step's impact needs.)  contact_report [B][4]: the
 // report of that plant step or NULL.  Outputs set on d.update are written as well.
 inline int detect_contacts(qlamd_context *ctx, PlantState &s, const ContactDetector &d, const uint8_t *contact_report, int32_t *status) {
   const qlamd_wholebody_batch in = s.batch();
-  qlamd_contact_update u = d.update;
-  u.contact_report = contact_report;
-  u.support_next = s.support_leg.data();
+  const qlamd_contact_update u = contact_update(s, d, contact_report);
   return qlamd_wholebody_contact_update_batch(ctx, &in, s.base_position.data(), &u, s.size(), status, QLAMD_MEM_HOST, nullptr);
 }
 

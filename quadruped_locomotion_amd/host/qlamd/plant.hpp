@@ -42,6 +42,17 @@ struct PlantState {
     in.support_leg = support_leg.data();
     return in;
   }
+  // the state as the output of a plant step: the step is taken in place
+  qlamd_plant_next next() {
+    qlamd_plant_next out;
+    out.joint_position = joint_position.data();
+    out.joint_velocity = joint_velocity.data();
+    out.base_position = base_position.data();
+    out.base_orientation = base_orientation.data();
+    out.base_linear_velocity = base_linear_velocity.data();
+    out.base_angular_velocity = base_angular_velocity.data();
+    return out;
+  }
   std::vector<double> joint_position, joint_velocity;          // [B][12]
   std::vector<double> base_position;                           // [B][3] world
   std::vector<double> base_orientation;                        // [B][4] (w, x, y, z)
@@ -65,18 +76,22 @@ inline int forward_dynamics(qlamd_context *ctx, const PlantState &s, const doubl
 inline int step(qlamd_context *ctx, PlantState &s, const double *joint_effort, double gravity, double dt, int32_t *status,
                 double *contact_force = nullptr, const double *generalized_force = nullptr) {
   const qlamd_wholebody_batch in = s.batch();
-  qlamd_plant_next next;
-  next.joint_position = s.joint_position.data();
-  next.joint_velocity = s.joint_velocity.data();
-  next.base_position = s.base_position.data();
-  next.base_orientation = s.base_orientation.data();
-  next.base_linear_velocity = s.base_linear_velocity.data();
-  next.base_angular_velocity = s.base_angular_velocity.data();
+  const qlamd_plant_next next = s.next();
   return qlamd_wholebody_forward_dynamics_batch(ctx, &in, joint_effort, generalized_force, s.base_position.data(), gravity, dt, s.size(),
                                                 nullptr, contact_force, &next, status, QLAMD_MEM_HOST, nullptr);
 }
 
 #ifdef QLAMD_HAS_PLANT_CONTACTS
+// The contacts struct of every step with contacts: the state's previous flags, k_v, mu and the report (or NULL); no other output
+inline qlamd_plant_contacts plant_contacts(const PlantState &s, double k_v, double friction, uint8_t *contact_report) {
+  qlamd_plant_contacts contacts{};
+  contacts.previous_support_leg = s.previous_support_leg.data();
+  contacts.velocity_gain = k_v;
+  contacts.friction_coefficient = friction;
+  contacts.contact_report = contact_report;
+  return contacts;
+}
+
 // One step of `dt` in place with contacts (qlamd_wholebody_plant_step_batch): the impact over the held feet of every robot one of
 // whose feet is flagged now and was not in the step before, the dynamics at nu+ with the velocity term k_v (1/s; 1/dt brings a held
 // foot to rest within the step), the state update from nu+.  contact_force [B][12] and contact_report [B][4] (QLAMD_CONTACT_* bits
@@ -85,18 +100,8 @@ inline int step_with_contacts(qlamd_context *ctx, PlantState &s, const double *j
                               int32_t *status, double *contact_force = nullptr, uint8_t *contact_report = nullptr,
                               double friction = 0.0, const double *generalized_force = nullptr) {
   const qlamd_wholebody_batch in = s.batch();
-  qlamd_plant_next next;
-  next.joint_position = s.joint_position.data();
-  next.joint_velocity = s.joint_velocity.data();
-  next.base_position = s.base_position.data();
-  next.base_orientation = s.base_orientation.data();
-  next.base_linear_velocity = s.base_linear_velocity.data();
-  next.base_angular_velocity = s.base_angular_velocity.data();
-  qlamd_plant_contacts contacts{};
-  contacts.previous_support_leg = s.previous_support_leg.data();
-  contacts.velocity_gain = k_v;
-  contacts.friction_coefficient = friction;
-  contacts.contact_report = contact_report;
+  const qlamd_plant_next next = s.next();
+  const qlamd_plant_contacts contacts = plant_contacts(s, k_v, friction, contact_report);
   const int rc = qlamd_wholebody_plant_step_batch(ctx, &in, joint_effort, generalized_force, s.base_position.data(), gravity, dt,
                                                   s.size(), nullptr, contact_force, &next, &contacts, status, QLAMD_MEM_HOST, nullptr);
   if (rc == QLAMD_OK) s.previous_support_leg = s.support_leg;

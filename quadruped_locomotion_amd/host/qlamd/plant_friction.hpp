@@ -20,18 +20,8 @@ inline int step_with_friction(qlamd_context *ctx, PlantState &s, const double *j
                               double friction, int32_t *status, double *contact_force = nullptr, uint8_t *contact_report = nullptr,
                               int32_t *iterations = nullptr, const double *generalized_force = nullptr) {
   const qlamd_wholebody_batch in = s.batch();
-  qlamd_plant_next next;
-  next.joint_position = s.joint_position.data();
-  next.joint_velocity = s.joint_velocity.data();
-  next.base_position = s.base_position.data();
-  next.base_orientation = s.base_orientation.data();
-  next.base_linear_velocity = s.base_linear_velocity.data();
-  next.base_angular_velocity = s.base_angular_velocity.data();
-  qlamd_plant_contacts contacts{};
-  contacts.previous_support_leg = s.previous_support_leg.data();
-  contacts.velocity_gain = k_v;
-  contacts.friction_coefficient = friction;
-  contacts.contact_report = contact_report;
+  const qlamd_plant_next next = s.next();
+  const qlamd_plant_contacts contacts = plant_contacts(s, k_v, friction, contact_report);
   qlamd_plant_friction fr{};
   fr.iterations = iterations;
   const int rc = qlamd_wholebody_plant_step_friction_batch(ctx, &in, joint_effort, generalized_force, s.base_position.data(), gravity,

@@ -1,15 +1,13 @@
 """ctypes binding of include/qlamd_plant_friction.h (the part of the C-ABI that qlamd.h includes at its end) -- the plant step with
 friction: contact impulses and forces inside the friction pyramid -- on the marshalling helpers of capi.py (one path:
-capi._plant_host / capi._plant_device) and the struct of plant_contacts.py.  Plumbing only.
+capi._plant_host / capi._plant_device_args) and the structs of plant_contacts.py (one place: plant_contacts._structs).  Plumbing only.
 
 The same layout as capi.py: the header's constants, its struct, its function (SIGNATURES), the wrappers.
 tests/test_plant_friction_cpu.py holds all of them against the header and the C compiler."""
 import ctypes as C
 
-import numpy as np
-
 from . import capi
-from .plant_contacts import OUTPUTS, PlantContacts, CONTACT_TOUCHDOWN  # noqa: F401  (the report byte is shared)
+from .plant_contacts import _structs, CONTACT_TOUCHDOWN  # noqa: F401  (the report byte is shared)
 
 # bits of qlamd_plant_contacts::contact_report that this entry adds (QLAMD_<name> in the header)
 CONTACT_SEPARATING, CONTACT_SLIDING = 8, 16
@@ -29,16 +27,7 @@ EXPORTS = tuple(SIGNATURES)
 
 def lib():
     """capi.lib() with this header's entry declared; a library without it is an error here (there is no fallback)."""
-    L = capi.lib()
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return L
-
-
-def _entry():
-    """the declared entry: what capi._plant_call is handed, so that it never reaches an undeclared function"""
-    return lib().qlamd_wholebody_plant_step_friction_batch
+    return capi.declared(SIGNATURES)
 
 
 def wholebody_plant_step_friction(ctx, state, tau, friction, g_ext=None, gravity=9.81, dt=None, free_flight=False, in_place=False,
@@ -48,19 +37,10 @@ def wholebody_plant_step_friction(ctx, state, tau, friction, g_ext=None, gravity
     friction = mu > 0 the constraint; the report holds CONTACT_TOUCHDOWN / CONTACT_SEPARATING / CONTACT_SLIDING and the result also
     has iterations int32 [B,2] (impulse QP, force QP) when `want` names it.  with_friction=False: the friction struct is NULL,
     which is plant_contacts.wholebody_plant_step with the same contacts struct."""
-    B = state["q"].shape[0]
-    if prev_stance is not None:
-        prev_stance = np.ascontiguousarray(prev_stance, dtype=np.uint8)
-        if prev_stance.shape != (B, 4):
-            raise ValueError("prev_stance must be [%d, 4]" % B)
-    extra = {key: np.zeros((B, n), dtype) for key, _, n, dtype in OUTPUTS if key in want}
-    pc = PlantContacts(capi._ptr(prev_stance), float(velocity_gain), float(friction), *[capi._ptr(extra.get(key)) for key, _, _, _ in OUTPUTS])
-    pf = None
-    if with_friction:
-        if "iterations" in want:
-            extra["iterations"] = np.zeros((B, 2), np.int32)
-        pf = PlantFriction(capi._ptr(extra.get("iterations")))
-    return capi._plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, contacts=(_entry(), pc, pf), extra=extra)
+    structs, extra = _structs(state["q"].shape[0], float(friction), velocity_gain, dict(prev_stance=prev_stance), want,
+                              PlantFriction if with_friction else None)
+    return capi._plant_host(ctx, state, tau, g_ext, gravity, dt, free_flight, in_place, lib().qlamd_wholebody_plant_step_friction_batch,
+                            structs[:2], extra)
 
 
 def wholebody_plant_step_friction_device(ctx, dstate, tau, status, friction, acc=None, f=None, g_ext=None, gravity=9.81, dt=0.0,
@@ -68,12 +48,8 @@ def wholebody_plant_step_friction_device(ctx, dstate, tau, status, friction, acc
                                          impulse=None, report=None, iterations=None, with_friction=True):
     """Same entry on torch CUDA tensors; asynchronous.  plant_contacts.wholebody_plant_step_device's arguments, friction = mu > 0,
     and iterations int32 [B,2]: a preallocated output or None."""
-    B = dstate["q"].shape[0]
-    for name, a, dtype, n in (("prev_stance", prev_stance, "uint8", 4), ("nu_plus", nu_plus, "float64", 18),
-                              ("impulse", impulse, "float64", 12), ("report", report, "uint8", 4), ("iterations", iterations, "int32", 2)):
-        if a is not None and not capi._is(a, dtype, n * B):
-            raise ValueError("%s must be a contiguous %s tensor of %d x %d elements" % (name, dtype, B, n))
-    pc = PlantContacts(capi._ptr(prev_stance), float(velocity_gain), float(friction), capi._ptr(nu_plus), capi._ptr(impulse),
-                       capi._ptr(report))
-    pf = PlantFriction(capi._ptr(iterations)) if with_friction else None
-    capi._plant_device(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream, contacts=(_entry(), pc, pf))
+    structs, _ = _structs(dstate["q"].shape[0], float(friction), velocity_gain,
+                          dict(prev_stance=prev_stance, nu_plus=nu_plus, impulse=impulse, report=report, iterations=iterations),
+                          friction_struct=PlantFriction if with_friction else None)
+    capi._plant_call(*capi._plant_device_args(ctx, dstate, tau, status, acc, f, g_ext, gravity, dt, next, free_flight, stream,
+                                              lib().qlamd_wholebody_plant_step_friction_batch, structs[:2]))

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import binding_checks as BC
 from conftest import ROOT, has_gpu
 
 
@@ -94,37 +95,13 @@ def test_output_arrays_are_validated_before_the_library_writes_into_them():
 
 # ---- the binding against the header and the compiler ------------------------------------------------------------------------
 HEADER = os.path.join(ROOT, "include", "qlamd.h")
-PARAMETER_KINDS = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double, "unsigned": C.c_uint}
-RETURN_KINDS = {"int": C.c_int, "void": None, "unsigned": C.c_uint, "size_t": C.c_size_t, "const char *": C.c_char_p}
-
-
-def header_declarations():
-    """[(return type, name, [parameter kind: "pointer" or a key of PARAMETER_KINDS])] of every function include/qlamd.h declares."""
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    out = []
-    for ret, name, params in re.findall(r"^(int|void|unsigned|size_t|const char \*) ?(qlamd_\w+)\(([^;{]*)\);", text, flags=re.M):
-        kinds = []
-        for prm in (x.strip() for x in params.split(",")):
-            if prm != "void":
-                kinds.append("pointer" if "*" in prm else " ".join(prm.split()[:-1]))
-        out.append((ret, name, kinds))
-    return out
 
 
 def test_signatures_match_header():
     """Every entry's restype / argtypes in capi.SIGNATURES against its declaration: arity and the kind of each parameter."""
     from quadruped_locomotion_amd import capi
-    decls = header_declarations()
-    assert len(decls) == len(capi.EXPORTS) == 44 and [name for _, name, _ in decls] == list(capi.EXPORTS)   # (in the header's order)
-    for ret, name, kinds in decls:
-        restype, argtypes = capi.SIGNATURES[name]
-        assert restype is RETURN_KINDS[ret], name
-        assert len(argtypes) == len(kinds), name
-        for i, (t, kind) in enumerate(zip(argtypes, kinds)):
-            if kind == "pointer":
-                assert t is C.c_void_p or issubclass(t, C._Pointer), (name, i)
-            else:
-                assert t is PARAMETER_KINDS[kind], (name, i, kind)
+    names = BC.signatures_match(capi, HEADER, typed_pointers=True)                  # (in the header's order)
+    assert len(names) == len(capi.EXPORTS) == 44
 
 
 def test_lib_declares_every_entry(capi):
@@ -145,37 +122,19 @@ def compiled(tmp_path_factory):
     """What the C compiler says about include/qlamd.h, asked by a program generated from capi.py's own classes and constants:
     {"sizeof <struct>" | "sizeof <struct> <member>" | "offsetof <struct> <member>" | "value <NAME>": integer}.  A member the
     header does not have does not compile."""
-    import subprocess
     from quadruped_locomotion_amd import capi
     defined = set(re.findall(r"^#define QLAMD_(\w+)\s", open(HEADER).read(), flags=re.M))
     constants = [n for n, v in vars(capi).items() if n.isupper() and type(v) is int and n in defined]
-    structs = dict(mirrors(capi), qlamd_state_record=None)
-    lines = []
-    for cname, cls in structs.items():
-        lines.append('printf("sizeof %s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for member in ([f[0] for f in cls._fields_] if cls else [f for _, f, _ in capi.FIELD_OF_KEY]):
-            lines.append('printf("sizeof %s %s %%zu\\n", sizeof(((%s *)0)->%s));' % (cname, member, cname, member))
-            lines.append('printf("offsetof %s %s %%zu\\n", offsetof(%s, %s));' % (cname, member, cname, member))
-    lines += ['printf("value %s %%lld\\n", (long long)(QLAMD_%s));' % (n, n) for n in constants]
-    d = tmp_path_factory.mktemp("layout")
-    (d / "layout.c").write_text('#include <stddef.h>\n#include <stdio.h>\n#include "qlamd.h"\nint main(void) {\n  %s\n  return 0;\n}\n'
-                                % "\n  ".join(lines))
-    subprocess.check_call(["gcc", "-std=c11", "-I" + os.path.join(ROOT, "include"), str(d / "layout.c"), "-o", str(d / "layout")])
-    out = subprocess.run([str(d / "layout")], capture_output=True, text=True, check=True, timeout=60).stdout
-    return {line.rsplit(" ", 1)[0]: int(line.rsplit(" ", 1)[1]) for line in out.splitlines()}, constants
+    structs = dict(mirrors(capi), qlamd_state_record=[f for _, f, _ in capi.FIELD_OF_KEY])
+    return BC.layout(HEADER, structs, constants, tmp_path_factory.mktemp("layout")), constants
 
 
 def test_struct_mirrors_match_compiler(compiled):
     from quadruped_locomotion_amd import capi
     layout, _ = compiled
     m = mirrors(capi)
-    declared = set(re.findall(r"^typedef struct (qlamd_\w+) \{", open(HEADER).read(), flags=re.M))
-    assert len(m) == 18 and set(m) == declared - {"qlamd_state_record"}          # (the record is checked below, through its offsets)
-    for cname, cls in m.items():
-        assert C.sizeof(cls) == layout["sizeof " + cname], cname
-        for member, ctype in cls._fields_:
-            assert getattr(cls, member).offset == layout["offsetof %s %s" % (cname, member)], (cname, member)
-            assert C.sizeof(ctype) == layout["sizeof %s %s" % (cname, member)], (cname, member)
+    assert len(m) == 18 and set(m) == BC.header_structs(HEADER) - {"qlamd_state_record"}   # (the record is checked below, through its offsets)
+    BC.mirrors_match(m, layout)
 
 
 def test_constants_match_compiler(compiled):

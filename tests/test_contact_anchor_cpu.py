@@ -20,12 +20,11 @@ import contact_update_reference as CUR  # noqa: E402
 import plant_contacts_reference as PCR  # noqa: E402
 import plant_friction_reference as PFR  # noqa: E402
 import plant_reference as PR  # noqa: E402
-from test_plant_contacts_cpu import NEXT, WB, Recorder, f64, p  # noqa: E402
+import binding_checks as BC  # noqa: E402
+from binding_checks import GCC, GXX, NEXT, WB, Recorder, f64, p  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "qlamd_contact_anchor.h")
 ENTRIES = ("qlamd_wholebody_contact_update_anchored_batch", "qlamd_wholebody_plant_step_anchored_batch")
-GCC = ["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include")]
-GXX = ["g++", "-std=c++17", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include")]
 DT, MU = CAR.PLANT_DT, CAR.PLANT_MU
 
 
@@ -188,20 +187,8 @@ def test_the_library_exports_the_entries():
 
 def test_the_binding_matches_the_header_and_the_compiler(tmp_path):
     from quadruped_locomotion_amd import build, contact_anchor as CA, contact_detection as CD, plant_friction as PF
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    decls = re.findall(r"^(int|void) ?(qlamd_\w+)\(([^;{]*)\);", text, flags=re.M)
-    assert [name for _, name, _ in decls] == list(CA.EXPORTS)
-    kinds_of = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double}
-    names = {}
-    for ret, name, params in decls:
-        restype, argtypes = CA.SIGNATURES[name]
-        assert restype is C.c_int and ret == "int"
-        prms = [x.strip() for x in params.split(",")]
-        kinds = ["pointer" if "*" in prm else " ".join(prm.split()[:-1]) for prm in prms]
-        assert len(kinds) == len(argtypes)
-        for i, (ctype, kind) in enumerate(zip(argtypes, kinds)):
-            assert ctype is (C.c_void_p if kind == "pointer" else kinds_of[kind]), (name, i, kind)
-        names[name] = [prm.split()[-1].lstrip("*") for prm in prms]
+    names = BC.signatures_match(CA, HEADER)
+    assert list(names) == list(ENTRIES) and all(CA.SIGNATURES[name][0] is C.c_int for name in names)
     # the siblings' parameters with the new struct behind theirs
     upd = CD.SIGNATURES["qlamd_wholebody_contact_update_batch"][1]
     got = CA.SIGNATURES[ENTRIES[0]][1]
@@ -211,24 +198,12 @@ def test_the_binding_matches_the_header_and_the_compiler(tmp_path):
     assert got[:13] == fr[:13] and got[13] is C.c_void_p and got[14:] == fr[13:]
     assert names[ENTRIES[1]][11:14] == ["contacts", "friction", "anchor"]
     structs = {"qlamd_contact_anchors": CA.ContactAnchors, "qlamd_plant_anchor": CA.PlantAnchor}
-    assert set(re.findall(r"^typedef struct (qlamd_\w+) \{", open(HEADER).read(), flags=re.M)) == set(structs)
-    lines = []
-    for cname, cls in structs.items():
-        lines.append('printf("sizeof.%s %%zu 0\\n", sizeof(%s));' % (cname, cname))
-        for member, _ in cls._fields_:
-            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, member, cname, member, cname, member))
-    lines.append('printf("REANCHORED %d 0\\n", QLAMD_CONTACT_EVENT_REANCHORED);')
-    (tmp_path / "layout.c").write_text('#include <stddef.h>\n#include <stdio.h>\n#include "qlamd_contact_anchor.h"\nint main(void) {\n  %s\n  return 0;\n}\n'
-                                       % "\n  ".join(lines))
-    subprocess.check_call(GCC + [str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")])
-    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True, timeout=60).stdout.split("\n")
-    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out if l}
-    for cname, cls in structs.items():
-        assert got["sizeof." + cname][0] == C.sizeof(cls), cname
-        for member, ctype in cls._fields_:
-            assert got["%s.%s" % (cname, member)] == (getattr(cls, member).offset, C.sizeof(ctype)), (cname, member)
-    assert C.sizeof(CA.ContactAnchors) == 16 and C.sizeof(CA.PlantAnchor) == 32
-    assert got["REANCHORED"][0] == CA.CONTACT_EVENT_REANCHORED == CAR.REANCHORED == 8
+    assert BC.header_structs(HEADER) == set(structs)
+    got = BC.layout(HEADER, structs, ["CONTACT_EVENT_REANCHORED"], tmp_path)
+    BC.mirrors_match(structs, got)
+    assert got["sizeof qlamd_contact_anchors"] == C.sizeof(CA.ContactAnchors) == 16
+    assert got["sizeof qlamd_plant_anchor"] == C.sizeof(CA.PlantAnchor) == 32
+    assert got["value CONTACT_EVENT_REANCHORED"] == CA.CONTACT_EVENT_REANCHORED == CAR.REANCHORED == 8
     assert CA.CONTACT_EVENT_REANCHORED & (CD.CONTACT_EVENT_TOUCHDOWN | CD.CONTACT_EVENT_RELEASED_PULL | CD.CONTACT_EVENT_RELEASED_GAP) == 0
     build.build()
     for name in ENTRIES:
@@ -365,21 +340,7 @@ def test_the_wrappers_marshal_every_struct(monkeypatch):
 def test_resources_are_what_design_states(tmp_path):
     """DESIGN.md 4.6g names the three kernels' registers, private segment and LDS; the figures are the code-object metadata of the
     unit compiled with the build's flags.  No private segment in any of them; the update keeps four wavefronts per SIMD."""
-    from tools import kernel_isa
-    text = open(os.path.join(ROOT, "DESIGN.md")).read()
-    path = kernel_isa.assemble("contact_anchor_kernel.hip", out=str(tmp_path / "contact_anchor_kernel.s"))
-    md = kernel_isa.meta(path)
-    asm = open(path).read()
-    seen = {}
-    for kernel in ("anchored_contact_update_kernel", "anchored_plant_contact_kernel", "anchored_plant_friction_kernel"):
-        m = re.search(r"`%s`: (\d+) VGPR, (\d+) AGPR, (\d+) B private segment, (\d+) B LDS" % kernel, text)
-        assert m, "DESIGN.md 4.6g does not state the resources of %s" % kernel
-        names = [k for k in md if kernel in k]
-        assert len(names) == 1, kernel
-        lds = re.search(r"\.group_segment_fixed_size:\s+(\d+)\n(?:(?!.*\.group_segment_fixed_size).*\n)*?\s+\.name:\s+%s\n" % re.escape(names[0]), asm)
-        got = [md[names[0]]["vgpr"], md[names[0]].get("agpr", 0), md[names[0]].get("scratch", 0), int(lds.group(1))]
-        assert got == [int(x) for x in m.groups()], (kernel, got)
-        assert got[2] == 0, kernel
-        seen[kernel] = got
-    assert len([k for k in md if "kernel" in k]) == 3
-    assert seen["anchored_contact_update_kernel"][0] <= 128            # 512 / 128: four wavefronts per SIMD
+    seen = BC.resources("contact_anchor_kernel.hip", ("anchored_contact_update_kernel", "anchored_plant_contact_kernel",
+                                                      "anchored_plant_friction_kernel"), 3, tmp_path)
+    assert all(got[2] == 0 for got, _ in seen.values())
+    assert seen["anchored_contact_update_kernel"][0][0] <= 128         # 512 / 128: four wavefronts per SIMD

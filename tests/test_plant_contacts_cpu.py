@@ -14,8 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import binding_checks as BC  # noqa: E402
 import plant_contacts_reference as PCR  # noqa: E402
 import plant_reference as PR  # noqa: E402
+from binding_checks import NEXT, WB, Recorder, f64, p  # noqa: E402
 
 DT = 0.0025
 MU = 0.6
@@ -143,34 +145,15 @@ def test_the_binding_matches_the_header_and_the_compiler(tmp_path):
     its row in SIGNATURES with the arity, the kind of each parameter and the return kind of the declaration; the struct mirror has
     the compiler's size and offsets; the constants have the header's values; the loaded library carries the declaration."""
     from quadruped_locomotion_amd import build, plant_contacts as PC
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    decls = re.findall(r"^(int|void) ?(qlamd_\w+)\(([^;{]*)\);", text, flags=re.M)
-    assert [name for _, name, _ in decls] == list(PC.EXPORTS) and len(decls) == 1
-    kinds_of = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double}
-    for ret, name, params in decls:
-        restype, argtypes = PC.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "void": None}[ret]
-        kinds = ["pointer" if "*" in prm else " ".join(prm.split()[:-1]) for prm in (x.strip() for x in params.split(","))]
-        assert len(kinds) == len(argtypes) == 15
-        for i, (ctype, kind) in enumerate(zip(argtypes, kinds)):
-            assert ctype is (C.c_void_p if kind == "pointer" else kinds_of[kind]), (name, i, kind)
-    assert set(re.findall(r"^typedef struct (qlamd_\w+) \{", open(HEADER).read(), flags=re.M)) == {"qlamd_plant_contacts"}
-    lines = ['printf("sizeof %zu\\n", sizeof(qlamd_plant_contacts));']
-    for member, _ in PC.PlantContacts._fields_:
-        lines.append('printf("%s %%zu %%zu\\n", offsetof(qlamd_plant_contacts, %s), sizeof(((qlamd_plant_contacts *)0)->%s));' % (member, member, member))
-    for n in ("CONTACT_PULLS", "CONTACT_OUTSIDE_CONE", "CONTACT_TOUCHDOWN"):
-        lines.append('printf("%s %%d 0\\n", QLAMD_%s);' % (n, n))
-    (tmp_path / "layout.c").write_text('#include <stddef.h>\n#include <stdio.h>\n#include "qlamd_plant_contacts.h"\nint main(void) {\n  %s\n  return 0;\n}\n'
-                                       % "\n  ".join(lines))
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")])
-    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True, timeout=60).stdout.split("\n")
-    assert int(out[0].split()[1]) == C.sizeof(PC.PlantContacts) == 48
-    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out[1:] if l}
-    for member, ctype in PC.PlantContacts._fields_:
-        assert got[member] == (getattr(PC.PlantContacts, member).offset, C.sizeof(ctype)), member
-    for n in ("CONTACT_PULLS", "CONTACT_OUTSIDE_CONE", "CONTACT_TOUCHDOWN"):
-        assert got[n][0] == getattr(PC, n)
+    names = BC.signatures_match(PC, HEADER)
+    assert len(names) == 1 and len(names["qlamd_wholebody_plant_step_batch"]) == 15
+    structs, constants = {"qlamd_plant_contacts": PC.PlantContacts}, ("CONTACT_PULLS", "CONTACT_OUTSIDE_CONE", "CONTACT_TOUCHDOWN")
+    assert BC.header_structs(HEADER) == set(structs)
+    got = BC.layout(HEADER, structs, constants, tmp_path)
+    BC.mirrors_match(structs, got)
+    assert got["sizeof qlamd_plant_contacts"] == C.sizeof(PC.PlantContacts) == 48
+    for n in constants:
+        assert got["value " + n] == getattr(PC, n)
     build.build()
     fn = PC.lib().qlamd_wholebody_plant_step_batch
     assert fn.restype is C.c_int and list(fn.argtypes) == PC.SIGNATURES["qlamd_wholebody_plant_step_batch"][1]
@@ -211,49 +194,7 @@ def test_the_cpp_wrapper_compiles_against_the_header(tmp_path):
                            "-I" + os.path.join(ROOT, "quadruped_locomotion_amd", "host"), "-c", str(src), "-o", str(tmp_path / "contacts.o")])
 
 
-# ---- what the wrappers hand to the entry (the recorder of tests/test_capi_marshalling_cpu.py, for this entry) -------------------
-
-class Recorder:
-    """Stands in for the loaded library: the plant-step entry records its arguments as the entry would see them while the call is
-    in progress -- scalars by value, the three structs read back member by member from the recorded byref -- and returns 0."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("qlamd_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, [self.snap(v) for v in args]))
-            return 0
-        fn.__name__ = name
-        return fn
-
-    @staticmethod
-    def snap(v):
-        if hasattr(v, "_obj"):
-            v = v._obj
-        if isinstance(v, C.Structure):
-            return {n: getattr(v, n) for n, _ in v._fields_}
-        return v.value if isinstance(v, C._SimpleCData) else v
-
-
-def p(a):
-    if a is None:
-        return None
-    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
-
-
-def f64(*shape):
-    return np.arange(int(np.prod(shape)), dtype=np.float64).reshape(shape) + 1.0
-
-
-WB = dict(q="joint_position", qd="joint_velocity", base_quat="base_orientation", base_linvel="base_linear_velocity",
-          base_angvel="base_angular_velocity", stance="support_leg", normals="surface_normal")
-NEXT = (("joint_position", "q"), ("joint_velocity", "qd"), ("base_position", "base_pos"), ("base_orientation", "base_quat"),
-        ("base_linear_velocity", "base_linvel"), ("base_angular_velocity", "base_angvel"))
-
+# ---- what the wrappers hand to the entry (tests/binding_checks.py's recorder) ---------------------------------------------------
 
 def test_the_wrappers_marshal_plant_contacts(monkeypatch):
     import torch
@@ -345,18 +286,5 @@ def test_the_wrappers_marshal_plant_contacts(monkeypatch):
 def test_resources_are_what_design_states(tmp_path):
     """DESIGN.md 4.6d names the new kernel's registers, private segment and LDS; the figures are the code-object metadata of the
     unit compiled with the build's flags."""
-    from tools import kernel_isa
-    text = open(os.path.join(ROOT, "DESIGN.md")).read()
-    m = re.search(r"`plant_contact_kernel`: (\d+) VGPR, (\d+) AGPR, (\d+) B private segment, (\d+) B LDS", text)
-    assert m, "DESIGN.md 4.6d does not state the kernel's resources"
-    stated = [int(x) for x in m.groups()]
-    path = kernel_isa.assemble("plant_contact_kernel.hip", out=str(tmp_path / "plant_contact_kernel.s"))
-    md = kernel_isa.meta(path)
-    names = [k for k in md if "plant_contact_kernel" in k]
-    assert len(names) == 1
-    name = names[0]
-    lds = [int(x) for x in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", open(path).read())]
-    assert len(lds) == 1
-    got = [md[name]["vgpr"], md[name].get("agpr", 0), md[name].get("scratch", 0), lds[0]]
-    assert got == stated, (got, stated)
-    assert md[name].get("scratch", 0) == 0
+    (got, _), = BC.resources("plant_contact_kernel.hip", ["plant_contact_kernel"], 1, tmp_path).values()
+    assert got[2] == 0

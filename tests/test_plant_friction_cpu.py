@@ -18,7 +18,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import plant_contacts_reference as PCR  # noqa: E402
 import plant_friction_reference as PFR  # noqa: E402
 import plant_reference as PR  # noqa: E402
-from test_plant_contacts_cpu import NEXT, WB, Recorder, f64, p  # noqa: E402
+import binding_checks as BC  # noqa: E402
+from binding_checks import NEXT, WB, Recorder, f64, p  # noqa: E402
 
 DT = 0.0025
 MU = 0.6
@@ -151,41 +152,20 @@ def test_the_library_exports_the_entry():
 
 def test_the_binding_matches_the_header_and_the_compiler(tmp_path):
     """What tests/test_plant_contacts_cpu.py holds plant_contacts.py to, for plant_friction.py and its header."""
-    from quadruped_locomotion_amd import build, plant_friction as PF
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    decls = re.findall(r"^(int|void) ?(qlamd_\w+)\(([^;{]*)\);", text, flags=re.M)
-    assert [name for _, name, _ in decls] == list(PF.EXPORTS) and len(decls) == 1
-    kinds_of = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double}
-    for ret, name, params in decls:
-        restype, argtypes = PF.SIGNATURES[name]
-        assert restype is {"int": C.c_int, "void": None}[ret]
-        kinds = ["pointer" if "*" in prm else " ".join(prm.split()[:-1]) for prm in (x.strip() for x in params.split(","))]
-        assert len(kinds) == len(argtypes) == 16
-        for i, (ctype, kind) in enumerate(zip(argtypes, kinds)):
-            assert ctype is (C.c_void_p if kind == "pointer" else kinds_of[kind]), (name, i, kind)
-        # the 15 parameters of the contacts entry with `friction` behind `contacts`
-        from quadruped_locomotion_amd import plant_contacts as PC
-        hard = PC.SIGNATURES["qlamd_wholebody_plant_step_batch"][1]
-        assert argtypes[:12] == hard[:12] and argtypes[12] is C.c_void_p and argtypes[13:] == hard[12:]
-        names = [prm.split()[-1].lstrip("*") for prm in (x.strip() for x in params.split(","))]
-        assert names[11:13] == ["contacts", "friction"]
-    assert set(re.findall(r"^typedef struct (qlamd_\w+) \{", open(HEADER).read(), flags=re.M)) == {"qlamd_plant_friction"}
-    lines = ['printf("sizeof %zu\\n", sizeof(qlamd_plant_friction));']
-    for member, _ in PF.PlantFriction._fields_:
-        lines.append('printf("%s %%zu %%zu\\n", offsetof(qlamd_plant_friction, %s), sizeof(((qlamd_plant_friction *)0)->%s));' % (member, member, member))
-    for n in ("CONTACT_SEPARATING", "CONTACT_SLIDING", "CONTACT_TOUCHDOWN"):
-        lines.append('printf("%s %%d 0\\n", QLAMD_%s);' % (n, n))
-    (tmp_path / "layout.c").write_text('#include <stddef.h>\n#include <stdio.h>\n#include "qlamd_plant_friction.h"\nint main(void) {\n  %s\n  return 0;\n}\n'
-                                       % "\n  ".join(lines))
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")])
-    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True, timeout=60).stdout.split("\n")
-    assert int(out[0].split()[1]) == C.sizeof(PF.PlantFriction) == 8
-    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out[1:] if l}
-    for member, ctype in PF.PlantFriction._fields_:
-        assert got[member] == (getattr(PF.PlantFriction, member).offset, C.sizeof(ctype)), member
-    for n in ("CONTACT_SEPARATING", "CONTACT_SLIDING", "CONTACT_TOUCHDOWN"):
-        assert got[n][0] == getattr(PF, n)
+    from quadruped_locomotion_amd import build, plant_contacts as PC, plant_friction as PF
+    names = BC.signatures_match(PF, HEADER)
+    assert len(names) == 1 and len(names[ENTRY]) == 16
+    # the 15 parameters of the contacts entry with `friction` behind `contacts`
+    argtypes, hard = PF.SIGNATURES[ENTRY][1], PC.SIGNATURES["qlamd_wholebody_plant_step_batch"][1]
+    assert argtypes[:12] == hard[:12] and argtypes[12] is C.c_void_p and argtypes[13:] == hard[12:]
+    assert names[ENTRY][11:13] == ["contacts", "friction"]
+    structs, constants = {"qlamd_plant_friction": PF.PlantFriction}, ("CONTACT_SEPARATING", "CONTACT_SLIDING", "CONTACT_TOUCHDOWN")
+    assert BC.header_structs(HEADER) == set(structs)
+    got = BC.layout(HEADER, structs, constants, tmp_path)
+    BC.mirrors_match(structs, got)
+    assert got["sizeof qlamd_plant_friction"] == C.sizeof(PF.PlantFriction) == 8
+    for n in constants:
+        assert got["value " + n] == getattr(PF, n)
     assert (PF.CONTACT_SEPARATING, PF.CONTACT_SLIDING) == (PFR.SEPARATING, PFR.SLIDING) == (8, 16)
     build.build()
     fn = getattr(PF.lib(), ENTRY)
@@ -291,19 +271,6 @@ def test_the_wrappers_marshal_both_structs(monkeypatch):
 def test_resources_are_what_design_states(tmp_path):
     """DESIGN.md 4.6f names the new kernel's registers, private segment and LDS; the figures are the code-object metadata of the
     unit compiled with the build's flags.  No private segment."""
-    from tools import kernel_isa
-    text = open(os.path.join(ROOT, "DESIGN.md")).read()
-    m = re.search(r"`plant_friction_kernel`: (\d+) VGPR, (\d+) AGPR, (\d+) B private segment, (\d+) B LDS", text)
-    assert m, "DESIGN.md 4.6f does not state the kernel's resources"
-    stated = [int(x) for x in m.groups()]
-    path = kernel_isa.assemble("plant_friction_kernel.hip", out=str(tmp_path / "plant_friction_kernel.s"))
-    md = kernel_isa.meta(path)
-    names = [k for k in md if "plant_friction_kernel" in k]
-    assert len(names) == 1
-    name = names[0]
-    lds = [int(x) for x in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", open(path).read())]
-    assert len(lds) == 1
-    got = [md[name]["vgpr"], md[name].get("agpr", 0), md[name].get("scratch", 0), lds[0]]
-    assert got == stated, (got, stated)
-    assert md[name].get("scratch", 0) == 0
-    assert not [l for l in kernel_isa.kernels(path)[name] if "scratch_" in l.split(";")[0]]
+    (got, lines), = BC.resources("plant_friction_kernel.hip", ["plant_friction_kernel"], 1, tmp_path).values()
+    assert got[2] == 0
+    assert not [l for l in lines if "scratch_" in l.split(";")[0]]
