@@ -106,7 +106,14 @@ void qlamd_balance_default_params(qlamd_balance_params *p);
  * [leg][segment] joint origin, fixed rpy, link mass and centre of mass.
  * Segments 0..2 are revolute about local z, segment 3 is the fixed foot.
  * Replaces kdl_parser::treeFromFile + tree_.getChain
- * (quadrupedkinematics.cpp:54-74). */
+ * (quadrupedkinematics.cpp:54-74).
+ * Link masses are >= 0.  A link of mass 0 (give it inertia 0 as well), such
+ * as the massless fixed foot link of many URDFs, contributes nothing to any
+ * entry: no force, no gravity torque, no inertia.  Every entry honours this.
+ * The masses of a leg's chain must not all be 0 (the whole-body entries
+ * need a positive definite mass matrix), and base_mass is > 0.  Nothing else
+ * is assumed of the numbers: inertia tensors may be full, every segment's
+ * rpy may be non-zero, and the four legs need not resemble each other. */
 typedef struct qlamd_robot_model {
   double joint_xyz[4][4][3];
   double joint_rpy[4][4][3];

@@ -45,15 +45,73 @@ def build(force=False):
 
 _lib = None
 _ref = None
+_model_headers = {}     # variant name -> text of its qlamd_robot_constants.h (register_model)
+_model_libs = {}        # variant name -> the loaded _models/<name>/liboracle.so
+_active_model = None    # None: the default liboracle.so
+
+
+def _load(path):
+    L = C.CDLL(path)
+    L.oracle_solve_quadprog.restype = C.c_int
+    L.oracle_leg_potential.restype = C.c_double
+    return L
 
 
 def lib():
+    """The library every function of this module calls: liboracle.so, or inside `with model(name):` that variant's."""
     global _lib
+    if _active_model is not None:
+        return _model_libs[_active_model]
     if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.oracle_solve_quadprog.restype = C.c_int
-        _lib.oracle_leg_potential.restype = C.c_double
+        _lib = _load(build())
     return _lib
+
+
+def register_model(name, header):
+    """Name a robot-model variant by the text of its qlamd_robot_constants.h-shaped header (tests/robot_models.py)."""
+    _model_headers[name] = header
+
+
+def build_model(name):
+    """Compile ORACLE_SRC against the variant's header: oracle/_models/<name>/liboracle.so, header beside it."""
+    d = os.path.join(_HERE, "_models", name)
+    hdr = os.path.join(d, "qlamd_robot_constants.h")
+    text = _model_headers.get(name)
+    if text is None and not os.path.exists(hdr):
+        raise KeyError("robot model %r is not registered (oracle.register_model)" % name)
+    if text is not None:
+        os.makedirs(d, exist_ok=True)
+        old = open(hdr).read() if os.path.exists(hdr) else None
+        if old != text:
+            with open(hdr, "w") as f:
+                f.write(text)
+    subprocess.check_call(["make", "-C", _HERE, "_models/%s/liboracle.so" % name], stdout=subprocess.DEVNULL)
+    return os.path.join(d, "liboracle.so")
+
+
+def active_model():
+    """Name of the model the module computes on right now ("default" outside every `with model(...)`)."""
+    return _active_model or "default"
+
+
+class model:
+    """`with model("skew"):` -- every function of this module (and so every reference that goes through it) computes on
+    that variant until the block ends; "default" or None is the default library.  Blocks nest."""
+
+    def __init__(self, name):
+        self.name = None if name in (None, "default") else name
+
+    def __enter__(self):
+        global _active_model
+        if self.name is not None and self.name not in _model_libs:
+            _model_libs[self.name] = _load(build_model(self.name))
+        self.previous, _active_model = _active_model, self.name
+        return self
+
+    def __exit__(self, *exc):
+        global _active_model
+        _active_model = self.previous
+        return False
 
 
 def ref_lib():

@@ -68,7 +68,8 @@ QL_HD void leg_rnea(const Tab &tab, const double q[3], const double qd[3], const
     QL_UNROLL for (int k = 0; k < 3; k++) {
       // m * c_b = m * p_b + R_b (m com)
       const double mc = R[b][3 * k] * tab[kTabMcom + 3 * b] + R[b][3 * k + 1] * tab[kTabMcom + 3 * b + 1] + R[b][3 * k + 2] * tab[kTabMcom + 3 * b + 2];
-      c[b][k] = p[b][k] + mc / m;
+      // a massless link (m = 0, so m com = 0) contributes no force; its centre is its origin, not 0 / 0
+      c[b][k] = p[b][k] + (m > 0.0 ? mc / m : 0.0);
       dc[k] = c[b][k] - p[i][k];
     }
     cross3(al[i], dc, axd); cross3(w[i], dc, wxd); cross3(w[i], wxd, wxwxd);

@@ -25,16 +25,17 @@ static void load(RobotIn &in, const double *q, const double *pos, const double *
   in.has_wrench = false;
 }
 
-extern "C" void mirror_balance_batch(const qlamd_balance_params *prm, int64_t B, const double *q,
-                                     const double *pos, const double *quat, const double *lv, const double *av,
-                                     const double *dpos, const double *dquat, const double *dlv,
-                                     const double *dav, const uint8_t *stance, const double *normals,
-                                     double *tau, double *grf, int32_t *status, int32_t *iters,
-                                     int32_t *n_active) {
-  qlamd_robot_model model;
-  default_robot_model(&model);
+// Every entry below that reads the robot model comes twice: `<name>_model` on a caller-given qlamd_robot_model
+// (tests/robot_models.py: full inertia tensors, rotated fixed segments, unequal legs, massless links), and `<name>` on the
+// default model through the same body.
+extern "C" void mirror_balance_batch_model(const qlamd_robot_model *model, const qlamd_balance_params *prm, int64_t B,
+                                           const double *q, const double *pos, const double *quat, const double *lv,
+                                           const double *av, const double *dpos, const double *dquat, const double *dlv,
+                                           const double *dav, const uint8_t *stance, const double *normals,
+                                           double *tau, double *grf, int32_t *status, int32_t *iters,
+                                           int32_t *n_active) {
   DeviceParams P;
-  build_device_params(*prm, model, &P);
+  build_device_params(*prm, *model, &P);
   for (int64_t i = 0; i < B; i++) {
     RobotIn in;
     load(in, q + 12 * i, pos + 3 * i, quat + 4 * i, lv + 3 * i, av + 3 * i, dpos + 3 * i, dquat + 4 * i,
@@ -55,15 +56,32 @@ extern "C" void mirror_balance_batch(const qlamd_balance_params *prm, int64_t B,
   }
 }
 
-extern "C" void mirror_leg_kinematics(const double *q3, int leg, const double *g, double *p, double *J,
-                                      double *Gq) {
-  qlamd_balance_params prm;
-  default_balance_params(&prm);
+extern "C" void mirror_balance_batch(const qlamd_balance_params *prm, int64_t B, const double *q,
+                                     const double *pos, const double *quat, const double *lv, const double *av,
+                                     const double *dpos, const double *dquat, const double *dlv,
+                                     const double *dav, const uint8_t *stance, const double *normals,
+                                     double *tau, double *grf, int32_t *status, int32_t *iters,
+                                     int32_t *n_active) {
   qlamd_robot_model model;
   default_robot_model(&model);
+  mirror_balance_batch_model(&model, prm, B, q, pos, quat, lv, av, dpos, dquat, dlv, dav, stance, normals, tau, grf, status,
+                             iters, n_active);
+}
+
+extern "C" void mirror_leg_kinematics_model(const qlamd_robot_model *model, const double *q3, int leg, const double *g,
+                                            double *p, double *J, double *Gq) {
+  qlamd_balance_params prm;
+  default_balance_params(&prm);
   DeviceParams P;
-  build_device_params(prm, model, &P);
+  build_device_params(prm, *model, &P);
   leg_kinematics(P.legtab + kTabPerLeg * leg, q3, g, p, J, Gq);
+}
+
+extern "C" void mirror_leg_kinematics(const double *q3, int leg, const double *g, double *p, double *J,
+                                      double *Gq) {
+  qlamd_robot_model model;
+  default_robot_model(&model);
+  mirror_leg_kinematics_model(&model, q3, leg, g, p, J, Gq);
 }
 
 extern "C" void mirror_sincos(double x, double *s, double *c) { sincos_reduced(x, *s, *c); }
@@ -197,30 +215,24 @@ extern "C" int mirror_robot_state_unpack(const uint8_t *msg, int64_t len, RobotS
 }
 
 // ---- analytic leg IK (row f4) ----
-extern "C" int mirror_leg_ik(int leg, const double *p_base, int config, const double *geom, double *q) {
+extern "C" int mirror_leg_ik_model(const qlamd_robot_model *model, int leg, const double *p_base, int config,
+                                   const double *geom, double *q) {
   qlamd_balance_params prm;
   default_balance_params(&prm);
+  DeviceParams P;
+  build_device_params(prm, *model, &P);
+  return leg_inverse_kinematics(P.legtab + kTabPerLeg * leg, p_base, config, geom, q) ? 1 : 0;
+}
+
+extern "C" int mirror_leg_ik(int leg, const double *p_base, int config, const double *geom, double *q) {
   qlamd_robot_model model;
   default_robot_model(&model);
-  DeviceParams P;
-  build_device_params(prm, model, &P);
-  return leg_inverse_kinematics(P.legtab + kTabPerLeg * leg, p_base, config, geom, q) ? 1 : 0;
+  return mirror_leg_ik_model(&model, leg, p_base, config, geom, q);
 }
 
 // ---- swing-leg torque (row a18) ----
 #include "swing_core.hpp"
-extern "C" void mirror_swing_leg(int leg, const SwingParamsDev *SP, const double *q_id, const double *q, const double *qd,
-                                 const double *qd_old, const double *tp, const double *tv, double *tau) {
-  qlamd_balance_params prm;
-  default_balance_params(&prm);
-  qlamd_robot_model model;
-  default_robot_model(&model);
-  DeviceParams P;
-  build_device_params(prm, model, &P);
-  swing_leg_torque(P.legtab + kTabPerLeg * leg, *SP, q_id, q, qd, qd_old, tp, tv, tau);
-}
-
-// the same arithmetic on a caller-given robot model (tests/test_rbdl_pin.py: the reference's RBDL test model)
+// (tests/test_rbdl_pin.py passes the reference's RBDL test model)
 extern "C" void mirror_swing_leg_model(const qlamd_robot_model *model, int leg, const SwingParamsDev *SP, const double *q_id,
                                        const double *q, const double *qd, const double *qd_old, const double *tp,
                                        const double *tv, double *tau) {
@@ -231,18 +243,34 @@ extern "C" void mirror_swing_leg_model(const qlamd_robot_model *model, int leg, 
   swing_leg_torque(P.legtab + kTabPerLeg * leg, *SP, q_id, q, qd, qd_old, tp, tv, tau);
 }
 
+extern "C" void mirror_swing_leg(int leg, const SwingParamsDev *SP, const double *q_id, const double *q, const double *qd,
+                                 const double *qd_old, const double *tp, const double *tv, double *tau) {
+  qlamd_robot_model model;
+  default_robot_model(&model);
+  mirror_swing_leg_model(&model, leg, SP, q_id, q, qd, qd_old, tp, tv, tau);
+}
+
+extern "C" void mirror_swing_branch_leg_model(const qlamd_robot_model *model, int leg, int leg_mode, const SwingParamsDev *SP,
+                                              const PidParamsDev *pid, const double *quat, const double *q_id,
+                                              const double *q, const double *qd, const double *qd_old, const double *tp,
+                                              const double *tv, const double *cmd, double period, double *e_last,
+                                              double *e_int, double *effort) {
+  qlamd_balance_params prm;
+  default_balance_params(&prm);
+  DeviceParams P;
+  build_device_params(prm, *model, &P);
+  swing_branch_leg(P.legtab + kTabPerLeg * leg, *SP, *pid, leg, leg_mode, quat, q_id, q, qd, qd_old, tp, tv, cmd, period,
+                   e_last, e_int, effort);
+}
+
 extern "C" void mirror_swing_branch_leg(int leg, int leg_mode, const SwingParamsDev *SP, const PidParamsDev *pid,
                                         const double *quat, const double *q_id, const double *q, const double *qd,
                                         const double *qd_old, const double *tp, const double *tv, const double *cmd,
                                         double period, double *e_last, double *e_int, double *effort) {
-  qlamd_balance_params prm;
-  default_balance_params(&prm);
   qlamd_robot_model model;
   default_robot_model(&model);
-  DeviceParams P;
-  build_device_params(prm, model, &P);
-  swing_branch_leg(P.legtab + kTabPerLeg * leg, *SP, *pid, leg, leg_mode, quat, q_id, q, qd, qd_old, tp, tv, cmd, period,
-                   e_last, e_int, effort);
+  mirror_swing_branch_leg_model(&model, leg, leg_mode, SP, pid, quat, q_id, q, qd, qd_old, tp, tv, cmd, period, e_last, e_int,
+                                effort);
 }
 
 extern "C" int mirror_qp6_solve(int p, int m, const double *G, const double *g0, const double *CE, double ce0,

@@ -4,7 +4,30 @@ import numpy as np
 import pytest
 
 
+def _rpy(r, p, y):
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    return (np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]]) @ np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
+            @ np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]]))
+
+
+def chain_at_zero(table, leg):
+    """Foot position and orientation at q = 0 straight from a model table: the product of Trans(xyz) Rz Ry Rx per segment."""
+    p, R = np.zeros(3), np.eye(3)
+    for k in range(4):
+        p = p + R @ table["joint_xyz"][leg, k]
+        R = R @ _rpy(*table["joint_rpy"][leg, k])
+    return p, R
+
+
 def test_fk_nominal_pose(oracle):
+    if oracle.active_model() != "default":      # the same statement on another model: the chain of its own table
+        import robot_models
+        for leg in range(4):
+            p, R = oracle.leg_fk(leg, [0.0, 0.0, 0.0])
+            pe, Re = chain_at_zero(robot_models.table(oracle.active_model()), leg)
+            assert np.allclose(R @ R.T, np.eye(3), atol=1e-12)
+            assert np.abs(p - pe).max() < 1e-14 and np.abs(R - Re).max() < 1e-14
+        return
     # at q = 0 the chain is T(xyz0) R0 T(0) R1 T(0.308) T(0.308,0,foot_z) with literal rpy
     for leg, (sx, sy, fz) in enumerate([(1, 1, 0.23), (1, -1, 0.22053), (-1, -1, 0.22053), (-1, 1, 0.23)]):
         p, R = oracle.leg_fk(leg, [0.0, 0.0, 0.0])

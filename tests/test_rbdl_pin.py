@@ -94,19 +94,30 @@ def robot_model_of(chain, cls):
 def test_product_arithmetic_on_host_reproduces_rbdl_torques(mirror, rbdl):
     """csrc/swing_core.hpp (host build) through the swing-leg entry's own formula: gains 0, and the oldest queue entry
     chosen so that its finite difference is the file's acceleration (model_test_header.cpp:417-431,460)."""
+    host_swing_reproduces_rbdl(mirror, rbdl, split_last_body=True)
+
+
+def test_product_arithmetic_on_host_takes_the_massless_segment_as_stored(mirror, rbdl):
+    """The same with the reference's model as it is stored: the fourth segment has no mass, and a zero-mass link
+    contributes nothing (qlamd_robot_model in include/qlamd.h) -- not 0 / 0."""
+    host_swing_reproduces_rbdl(mirror, rbdl, split_last_body=False)
+
+
+def host_swing_reproduces_rbdl(mirror, rbdl, split_last_body):
     from quadruped_locomotion_amd import capi
-    model = robot_model_of(chain_of(rbdl, True), capi.RobotModel)
+    model = robot_model_of(chain_of(rbdl, split_last_body), capi.RobotModel)
     sp = _SP((0.0,) * 3, (0.0,) * 3, 1.0, 1.0, 1.0, 9.81)
     rows = np.arange(0, 10001, 7)
     worst = 0.0
     zero = np.zeros(3)
+    Q, QD, QDD, TAU = (rbdl[k] for k in ("q", "qd", "qdd", "tau"))     # (an .npz member is read anew at every access)
     for i in rows:
-        q, qd = rbdl["q"][i].copy(), rbdl["qd"][i].copy()
-        qd_old = qd - rbdl["qdd"][i]
+        q, qd = Q[i].copy(), QD[i].copy()
+        qd_old = qd - QDD[i]
         tau = np.zeros(3)
         mirror.L.mirror_swing_leg_model(C.byref(model), 0, C.byref(sp), _p(q)[1], _p(q)[1], _p(qd)[1], _p(qd_old)[1],
                                         _p(zero)[1], _p(zero)[1], tau.ctypes.data_as(_dp))
-        worst = max(worst, relative_deviation(tau, rbdl["tau"][i]))
+        worst = max(worst, relative_deviation(tau, TAU[i]))
     assert worst <= PRINT_PRECISION * 1.01      # qd - (qd - qdd) differs from qdd in the last bit
 
 
@@ -135,6 +146,29 @@ def test_swing_kernel_reproduces_all_rbdl_torques(rbdl):
     tau2 = capi.swing_leg_torque(ctx, q, qd, qd_old2, zero, zero, support, params=prm)
     assert relative_deviation(tau2[:, 0:3], rbdl["tau"]) <= PRINT_PRECISION * 1.01
     ctx.close()
+
+
+@pytest.mark.gpu
+def test_swing_kernel_takes_the_massless_segment_as_stored(rbdl):
+    """The GPU entry on the reference's model as stored (massless fourth segment), every 7th row, all four legs."""
+    from quadruped_locomotion_amd import capi
+    rows = np.arange(0, 10001, 7)
+    B = rows.size
+    ctx = capi.Context(model=robot_model_of(chain_of(rbdl, False), capi.RobotModel))
+    prm = capi.default_swing_params()
+    for k in range(3):
+        prm.kp[k] = 0.0
+        prm.kd[k] = 0.0
+    prm.period, prm.accel_window, prm.accel_scale, prm.gravity = 1.0, 1.0, 1.0, 9.81
+    q = np.tile(rbdl["q"][rows], (1, 4))
+    qd = np.tile(rbdl["qd"][rows], (1, 4))
+    qd_old = np.tile(rbdl["qd"][rows] - rbdl["qdd"][rows], (1, 4))
+    zero = np.zeros((B, 12))
+    tau = capi.swing_leg_torque(ctx, q, qd, qd_old, zero, zero, np.zeros((B, 4), dtype=np.uint8), params=prm)
+    ctx.close()
+    assert np.isfinite(tau).all()
+    for leg in range(4):
+        assert relative_deviation(tau[:, 3 * leg:3 * leg + 3], rbdl["tau"][rows]) <= PRINT_PRECISION * 1.01
 
 
 def test_wholebody_recursion_agrees_with_the_pinned_chain_recursion(oracle):

@@ -30,11 +30,22 @@ def test_mass_matrix_symmetric_pd_and_consistent_with_inverse_dynamics(oracle):
         full = oracle.wb_inverse_dynamics(q, quat, nu[i], nud[i], G)
         assert np.abs(M @ nud[i] + h - full).max() < 1e-10 * max(1.0, np.abs(full).max())
         # total mass on the linear block
-        m_tot = 27.801 + sum(sum(row) for row in _link_masses())
+        m_tot = _base_mass(oracle) + sum(sum(row) for row in _link_masses(oracle))
         assert np.allclose(M[:3, :3], m_tot * np.eye(3), atol=1e-12)
 
 
-def _link_masses():
+def _base_mass(oracle):
+    """27.801 on the default model; under `with oracle.model(name)` (tests/test_model_variants_cpu.py) that table's."""
+    if oracle.active_model() == "default":
+        return 27.801
+    import robot_models
+    return float(robot_models.table(oracle.active_model())["base_mass"])
+
+
+def _link_masses(oracle):
+    if oracle.active_model() != "default":
+        import robot_models
+        return robot_models.table(oracle.active_model())["link_mass"].tolist()
     import re, os
     txt = open(os.path.join(os.path.dirname(__file__), "..", "include", "qlamd_robot_constants.h")).read()
     blk = txt[txt.index("QLAMD_LINK_MASS"):]
