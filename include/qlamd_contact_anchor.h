@@ -93,4 +93,8 @@ int qlamd_wholebody_plant_step_anchored_batch(qlamd_context *ctx, const qlamd_wh
 }
 #endif
 
+/* the swing-foot task (QLAMD_HAS_SWING_TASK, qlamd_wholebody_swing_task_batch): part of this interface, kept in a file of its own
+ * that ships beside this one */
+#include "qlamd_swing_task.h"
+
 #endif /* QLAMD_CONTACT_ANCHOR_H */

@@ -12,7 +12,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB = os.path.join(_PKG, "libqlamd.so")
 SOURCE_NAMES = ("balance_kernel.hip", "pose_kernel.hip", "tick_kernel.hip", "wholebody_kernel.hip",
                 "plant_kernel.hip", "plant_contact_kernel.hip", "contact_update_kernel.hip", "plant_friction_kernel.hip",
-                "contact_anchor_kernel.hip")
+                "contact_anchor_kernel.hip", "swing_task_kernel.hip")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in SOURCE_NAMES]
 OBJ_DIR = os.path.join(_PKG, "csrc", "_obj")
 # Code-generation flags per translation unit.  The active-set kernels are single-wavefront latency problems (a
@@ -33,7 +33,7 @@ def headers():
     return [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith(".hpp")] + [
         os.path.join(_ROOT, "include", f) for f in ("qlamd.h", "qlamd_robot_constants.h", "qlamd_plant_contacts.h",
                                                     "qlamd_contact_detection.h", "qlamd_plant_friction.h",
-                                                    "qlamd_contact_anchor.h")]
+                                                    "qlamd_contact_anchor.h", "qlamd_swing_task.h")]
 
 
 def hipcc():

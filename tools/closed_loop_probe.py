@@ -40,9 +40,19 @@
    the run: |gap| of the held feet (largest and median), their distance |p - anchor| from the anchor the tick ran with, and the
    events per robot and tick, re-anchorings included.
 
+7. --swing (implies --detect; with or without --friction and --anchor): FOUR launches per tick.  In front of the whole-body step
+   qlamd_wholebody_swing_task_batch turns the trot's schedule (a leg the phase does not flag is to swing) and a foothold per swing
+   -- the foot where the swing begins plus the desired base velocity x T / 2, on the ground z = 0 -- into desired joint
+   accelerations and the flags the SOLVE runs with; the plant and the update keep the detected flags.  T is the trot's swing time,
+   the profile 0.08 m high; --swing-gains KP,KD (default 400,40), the error clamped to 0.05 m, lambda 0.05, |qdd| <= 500, a landing
+   counted from half the swing on, touchdown speed 0.1 m/s.  Part 1 times the new launch alone, every output given, next to the
+   contact update's (a device copy of the records goes in front of every timed launch, so that each begins the same swings, and is
+   timed alone beside it).  Part 2 also reports the task's events per tick and robot and, with or without --swing, the apex clearance:
+   per (robot, leg) the largest gap seen on the ticks the schedule wants the leg in the air.
+
 usage: closed_loop_probe.py [--batch 4096] [--ticks 64] [--batches 4096,65536,1048576] [--steps 64] [--repeats 5] [--out file]
                             [--contacts] [--velocity-gain K] [--detect] [--terrain plane|heightfield] [--friction]
-                            [--anchor] [--position-gain KP] [--max-error E]"""
+                            [--anchor] [--position-gain KP] [--max-error E] [--swing] [--swing-gains KP,KD]"""
 import argparse
 import os
 import sys
@@ -70,8 +80,10 @@ def main():
     ap.add_argument("--anchor", action="store_true")
     ap.add_argument("--position-gain", type=float, default=0.1 / DT ** 2)
     ap.add_argument("--max-error", type=float, default=0.01)
+    ap.add_argument("--swing", action="store_true")
+    ap.add_argument("--swing-gains", default="400,40")
     a = ap.parse_args()
-    a.detect = a.detect or a.anchor
+    a.detect = a.detect or a.anchor or a.swing
     a.contacts = a.contacts or a.detect or a.friction
     import torch
     from quadruped_locomotion_amd import capi, plant_contacts, synth
@@ -81,7 +93,12 @@ def main():
         from quadruped_locomotion_amd import plant_friction
     if a.anchor:
         from quadruped_locomotion_amd import contact_anchor
+    if a.swing:
+        from quadruped_locomotion_amd import swing_task
     MU = 0.6
+    SWING = dict(swing_duration=synth.T_SWING, profile_height=0.08, touchdown_speed=0.1, touchdown_phase=0.5, max_error=0.05, damping=0.05,
+                 max_joint_acceleration=500.0, dt=DT, position_gain=float(a.swing_gains.split(",")[0]),
+                 velocity_gain=float(a.swing_gains.split(",")[1]))
     ctx = capi.Context(device=0)
     stream = torch.cuda.current_stream().cuda_stream
     dev = dict(device="cuda:0")
@@ -181,6 +198,30 @@ def main():
                 "%d written)   status OK %d / %d   | qlamd_wholebody_dynamics_batch %.0f GB/s of its 4464 B written + 304 B read per robot"
                 % (B, a.terrain, t_upd[0], t_upd[1], B * per / t_upd[0] * 1e-3, per, per - UPDATE_BYTES[1], UPDATE_BYTES[1],
                    int((st == 0).sum()), B, B * 4768 / t_dyn[0] * 1e-3))
+            if a.swing:
+                u8 = lambda: torch.zeros(B, 4, dtype=torch.uint8, **dev)  # noqa: E731
+                dd["a_des"] = d["a_des"]
+                want1 = 1 - dd["stance"]
+                hold = o["foot_pos"].clone()    # (the update above left the feet there) every scheduled leg begins: 5 cm ahead, on the ground
+                hold.reshape(B, 4, 3)[:, :, 0] += 0.05
+                hold.reshape(B, 4, 3)[:, :, 2] = 0.0
+                records, rec0 = f64(B, 16), f64(B, 16)
+                rec0.reshape(B, 4, 4)[:, :, 3] = torch.from_numpy(np.random.default_rng(5).choice([0.0, 0.1, 0.3], size=(B, 4))).to("cuda:0")
+                rec0.reshape(B, 4, 4)[:, :, :3] = o["foot_pos"].reshape(B, 4, 3)
+                call = swing_task.SwingTaskCall(ctx, dd, st, want1, hold, records, f64(B, 12), normals=o["normals"], support_solve=u8(),
+                                                foot_reference=f64(B, 36), events=u8(), stream=stream, **SWING)   # checked once
+
+                def one_tick():      # (the records are put back every launch, so that each does the same work: one more copy of 128 B)
+                    records.copy_(rec0)
+                    call()
+                t_copy = sample(lambda: records.copy_(rec0), n)
+                t_sw = sample(one_tick, n)
+                per_sw = (296 + 4 + 48 + 4 + 96 + 96 + 128, 96 + 4 + 4 + 288 + 128 + 4)   # read: state, flags, a_des, schedule, footholds, normals, records
+                say("%8d robots: qlamd_wholebody_swing_task_batch (every input and output) %8.2f (%.2f) with a %.2f copy of the records in front "
+                    "= %.0f GB/s of its %d B per robot (%d read, %d written)   status OK %d / %d   | the contact update %8.2f"
+                    % (B, t_sw[0], t_sw[1], t_copy[0], B * sum(per_sw) / max(t_sw[0] - t_copy[0], 1e-3) * 1e-3, sum(per_sw), per_sw[0], per_sw[1],
+                       int((st == 0).sum()), B, t_upd[0]))
+                del call, records, rec0, hold, want1
             if a.anchor:
                 anchor = f64(B, 12)
                 call = contact_anchor.AnchoredContactUpdateCall(ctx, dd, st, anchor, reanchor_mask=16, report=report, stream=stream,
@@ -243,6 +284,10 @@ def main():
         s = dict(s, base_pos=(d0["base_pos"] - torch.stack([torch.zeros_like(lift), torch.zeros_like(lift), lift], dim=1)).cpu().numpy())
         ter = terrain(B)
         disagree = []
+        want_all = (1 - stance).contiguous()            # the schedule: a leg the trot's phase does not flag is to swing
+        step = torch.from_numpy(np.ascontiguousarray(s["des_linvel"] * (0.5 * synth.T_SWING))).to("cuda:0")
+        step[:, 2] = 0.0
+        footholds, swing_events, apex = [], [], torch.full((B, 4), -float("inf"), dtype=torch.float64, **dev)
 
     def loop(timed):
         d = capi.to_device(s)
@@ -263,6 +308,16 @@ def main():
                 update = contact_detection.ContactUpdateCall(ctx, d, st_up, report=report, stream=stream, support_next=d["stance"],
                                                              sensor=o["sensor"], events=o["events"], gap=o["gap"], normals=d["normals"],
                                                              **ter, **RULE)   # checked once; the tick launches it
+            if a.swing:
+                records, qdd, sup, sw_ev = f64(B, 16), f64(B, 12), zero_flags.clone(), zero_flags.clone()
+                st_sw = torch.zeros(B, dtype=torch.int32, **dev)
+                d_solve = dict(d, stance=sup, qdd_des=qdd)     # the solve's flags and accelerations; the plant keeps d["stance"]
+                fh_now, fp_now = f64(B, 12), f64(B, 12)
+
+                def swing_call(k):
+                    return swing_task.SwingTaskCall(ctx, d, st_sw, want_all[k], footholds[k], records, qdd, normals=d["normals"], support_solve=sup,
+                                                    events=sw_ev, stream=stream, **SWING)
+                swing_calls = [swing_call(k) for k in range(len(footholds))]   # (a timed loop: the footholds of the loop that went before)
         tau, st_qp, st_pl = f64(B, 12), torch.zeros(B, dtype=torch.int32, **dev), torch.zeros(B, dtype=torch.int32, **dev)
         mem, ws = torch.zeros(B, 4, dtype=torch.int64, **dev), torch.zeros(B, dtype=torch.int64, **dev)
         prev_ws = torch.zeros_like(ws)
@@ -270,8 +325,10 @@ def main():
         stats = []
 
         def tick(k):
+            if a.swing:
+                swing_calls[k]()
             if a.detect:
-                capi.wholebody_solve_placed_device(ctx, d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
+                capi.wholebody_solve_placed_device(ctx, d_solve if a.swing else d, tau, None, st_qp, stream=stream, working_set=ws, set_memory=mem)
                 if a.anchor:
                     contact_anchor.wholebody_plant_step_anchored_device(ctx, d, tau, st_pl, anchor, a.position_gain, max_error=a.max_error,
                                                                         friction=MU, cone=a.friction, dt=DT, next=d, stream=stream,
@@ -309,8 +366,21 @@ def main():
         for k in range(K):
             ran_with = d["stance"].clone() if a.detect else stance[k]
             held_at = anchor.clone() if a.anchor else None
+            if a.swing:
+                # the foothold of a swing that begins now: the foot where it is (one more update, outside the tick) plus the step
+                contact_detection.wholebody_contact_update_device(ctx, d, st_sw, stream=stream, foot_pos=fp_now, **ter)
+                begins = (want_all[k] != 0) & ((want_all[k - 1] == 0) if k else torch.ones_like(want_all[0], dtype=torch.bool))
+                target = fp_now.reshape(B, 4, 3) + step[:, None, :]
+                target[:, :, 2] = 0.0
+                fh_now.copy_(torch.where(begins[:, :, None], target, fh_now.reshape(B, 4, 3)).reshape(B, 12))
+                footholds.append(fh_now.clone())
+                swing_calls.append(swing_call(k))
             tick(k)
             torch.cuda.synchronize()
+            if a.swing:
+                swing_events.append(tuple(int((sw_ev & b).ne(0).sum()) for b in (1, 2, 4, 8)) + (int((st_sw == 0).sum()),))
+            if a.detect:
+                apex.copy_(torch.maximum(apex, torch.where(want_all[k] != 0, o["gap"], torch.full_like(apex, -float("inf")))))
             if a.anchor:
                 on_ = ran_with != 0
                 gap_ = o["gap"][on_].abs()
@@ -351,6 +421,20 @@ def main():
             % (np.mean([x[0] for x in disagree]), np.mean([x[0] for x in disagree[:max(1, K // 4)]]), np.mean([x[0] for x in disagree[-max(1, K // 4):]]),
                np.mean([x[1] for x in disagree]) / B, np.mean([x[2] for x in disagree]) / B, np.mean([x[3] for x in disagree]) / B,
                np.mean([x[4] for x in disagree]) / B))
+    if a.detect:
+        top = apex[torch.isfinite(apex)]
+        say("  apex clearance: over the %d (robot, leg) pairs the schedule wants in the air at some tick, the largest gap on those ticks: "
+            "median %.4f m, largest %.4g m, share above 0.02 m %.4f, share never above 0.001 m %.4f"
+            % (top.numel(), float(top.median()), float(top.max()), float((top > 0.02).float().mean()), float((top <= 0.001).float().mean())))
+    if a.swing:
+        say("  four launches per tick: qlamd_wholebody_swing_task_batch in front (T %.2f s, h %.2f m, k_p %g, k_d %g, e_max %g, lambda %g, "
+            "|qdd| <= %g); the solve runs with its flags and accelerations" % (SWING["swing_duration"], SWING["profile_height"], SWING["position_gain"],
+                                                                               SWING["velocity_gain"], SWING["max_error"], SWING["damping"], SWING["max_joint_acceleration"]))
+        q4 = max(1, K // 4)
+        for lo in range(0, K, q4):
+            part = swing_events[lo:lo + q4]
+            say("  ticks %3d-%3d: swing task OK %.4f; per tick and robot: began %.4f, landed %.4f, late lift-off %.4f, overtime %.4f"
+                % (lo, lo + len(part) - 1, np.mean([x[4] for x in part]) / B, *[np.mean([x[j] for x in part]) / B for j in range(4)]))
     if a.anchor:
         say("  the update and the plant step are the anchored entries: k_p %g / s^2, e_max %g m, %s; per quarter of the run, over the feet "
             "each tick's plant step held:" % (a.position_gain, a.max_error, "a sliding foot is re-anchored" if a.friction else "no re-anchoring"))
@@ -362,7 +446,7 @@ def main():
                 % (lo, lo + len(part) - 1, max(x[0] for x in part), float(np.median([x[1] for x in part])), max(x[2] for x in part),
                    float(np.median([x[3] for x in part])), np.mean([x[1] for x in ev]) / B, np.mean([x[2] for x in ev]) / B,
                    np.mean([x[3] for x in ev]) / B, np.mean([x[4] for x in part]) / B))
-    say("  us per tick (%s launches): %s median %.2f spread %.2f" % ("three" if a.detect else "two", " ".join("%.2f" % x for x in t), float(np.median(t)), max(t) - min(t)))
+    say("  us per tick (%s launches): %s median %.2f spread %.2f" % ("four" if a.swing else "three" if a.detect else "two", " ".join("%.2f" % x for x in t), float(np.median(t)), max(t) - min(t)))
     q = max(1, K // 4)
     for lo in range(0, K, q):
         part = stats[lo:lo + q]
